@@ -175,6 +175,51 @@ def cpu_baseline(params, frames, budget_s=30.0):
                       "is not installed) + C++ decode/wnms restatement" % len(times)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pipe, outs, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what a caller of the timed path receives for the batch `pipe` ran last, as out_dir/<name>.npy.  Per class
+    (names suffixed _<class> when the configuration has more than one): the graph's fg_cls_score (B, k) and decoded_bbox (B, k, 10),
+    and per frame the weighted NMS's results, frames concatenated in batch order -- wnms_rows (sum M, 12), keep_inds (sum M),
+    det_xyzlwhyaws (sum M, 8), num_kept (B), num_candidates (B).  Integers are stored as float64 (exact).  When everything would
+    exceed `budget` bytes, fg_cls_score / decoded_bbox keep the same fixed, seeded subset of candidate columns (sorted indices in
+    candidate_index[_<class>].npy).  Returns a summary for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget -= 4096                    # (the .npy headers, 128 bytes per file)
+    classes = pipe.class_names
+    arrays, big = {}, {}
+    for ci, c in enumerate(classes):
+        sfx = "" if len(classes) == 1 else "_" + c
+        frames = pipe.bposts[c].collect_all()
+        arrays["wnms_rows" + sfx] = np.concatenate([f["wnms_rows"].reshape(-1, 12) for f in frames]).astype(np.float32)
+        arrays["keep_inds" + sfx] = np.concatenate([f["keep_inds"].reshape(-1) for f in frames]).astype(np.float64)
+        arrays["det_xyzlwhyaws" + sfx] = np.concatenate([f["det_xyzlwhyaws"].reshape(-1, 8) for f in frames]).astype(np.float32)
+        arrays["num_kept" + sfx] = np.array([len(f["keep_inds"]) for f in frames], np.float64)
+        arrays["num_candidates" + sfx] = np.array([f["num_candidates"] for f in frames], np.float64)
+        big[sfx] = (outs[1 + 3 * ci].float().cpu().numpy(), outs[2 + 3 * ci].float().cpu().numpy())
+    fixed = sum(a.nbytes for a in arrays.values())
+    large = sum(s.nbytes + b.nbytes for s, b in big.values())
+    if fixed >= budget:
+        raise RuntimeError("--dump-outputs: the NMS results alone take %d bytes, more than %d" % (fixed, budget))
+    # fraction of candidate columns that fits (the index files of a sample are counted too: 8 bytes per kept column)
+    frac = min(1.0, (budget - fixed) / float(large + 8 * sum(s.shape[1] for s, _ in big.values())))
+    sampled = frac < 1.0
+    for sfx, (sc, bx) in big.items():
+        if sampled:
+            k = sc.shape[1]
+            idx = np.sort(np.random.default_rng(seed).choice(k, int(k * frac), replace=False))
+            sc, bx = sc[:, idx], bx[:, idx]
+            arrays["candidate_index" + sfx] = idx.astype(np.float64)
+        arrays["fg_cls_score" + sfx] = np.ascontiguousarray(sc, dtype=np.float32)
+        arrays["decoded_bbox" + sfx] = np.ascontiguousarray(bx, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= budget, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(arrays), "bytes": int(total), "candidates_sampled": sampled}
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -281,12 +326,18 @@ def main(argv=None):
                     help="replays of the Meta-Kernel + DLA backbone steps for the `meta_dla_forward` block (0: skip that block -- the rocprofv3 / PMC "
                          "passes of tools/profile_round.sh use 0 so that every profiled launch belongs to a full forward and the per-kernel averages "
                          "are those of the `roofline` block)")
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the timed region of --steps steps (barrier + synchronize on both sides) is run this many times back to back; "
                          "`value` / `ms_per_step` are the MEDIAN region, the spread is reported next to it (SURVEY.md 8d: median + p5/p95).  "
-                         "0 (default): as many regions as it takes for --min-timed-s seconds of timed GPU work (at least 5, at most 200), decided "
-                         "from the first region -- so that the run is long enough for an outside utilisation sampler to see it")
+                         "1 (default): one region, so that --steps is the number of timed steps.  0: as many regions as it takes for "
+                         "--min-timed-s seconds of timed GPU work (at least 5, at most 200), decided from the first region -- so that the run "
+                         "is long enough for an outside utilisation sampler to see it")
     ap.add_argument("--min-timed-s", type=float, default=15.0, help="with --repeats 0: total duration of the timed regions to aim for")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's batch) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all: per class the graph's sorted scores and decoded boxes (a fixed, seeded sample of candidates "
+                         "when the whole would not fit) and every frame's weighted-NMS results.  Inputs and weights are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
     args = ap.parse_args(argv)
     argv = list(sys.argv[1:] if argv is None else argv)
 
@@ -439,11 +490,12 @@ def main(argv=None):
             with multi.stream_context(j):
                 for k, v in host_in[i % len(frames)].items():
                     dev_in[j][k].copy_(v, non_blocking=True)
-            j2, _ = multi.enqueue(dev_in[j])
+            j2, outs = multi.enqueue(dev_in[j])
         else:
-            j2, _ = multi.enqueue(frames[i % len(frames)])
+            j2, outs = multi.enqueue(frames[i % len(frames)])
         assert j2 == j
         pj, h = multi.pipes[j], host[j]
+        h["outs"] = outs                                   # the graph's outputs (this pipeline's buffers) for --dump-outputs
         with torch.cuda.stream(pj._post_stream):
             for c in classes:
                 bp, hc = pj.bposts[c], h[c]
@@ -558,6 +610,11 @@ def main(argv=None):
             rows_, M_ = got[f_]
             want_ = lastf[b_]["wnms_rows"][:rdist.MAX_DET]
             gather_matches_local = gather_matches_local and M_ == len(lastf[b_]["wnms_rows"]) and np.array_equal(rows_.view(np.uint32), want_.view(np.uint32))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the profiling replay below, which runs pipeline 0 again and overwrites its buffers
+        assert host[last]["step"] == total_steps - 1
+        dumped = dump_outputs(args.dump_outputs, multi.pipes[last], host[last]["outs"])
 
     # ---- per-kernel timing with HIP events on the launch stream, over a replay of the same steps ------------------
     roof = meta_info = prof = backbone_info = block_info = None
@@ -700,6 +757,7 @@ def main(argv=None):
                        "results_to_host": "every step: (B,200,8) boxes + counts, async D2H on the post-processing stream into pinned memory, K <= cap checked",
                        "gathered_frames_last_step": gathered_frames, "gather_matches_local": gather_matches_local,
                        "results_sha256_last_step": results_sha256, "results_sha256_all_steps": all_steps_sha.hexdigest()[:16],
+                       "dumped_outputs": dumped,
                        "step_digests": step_digests if os.environ.get("RD_BENCH_STEP_DIGESTS") else None, "ranks_seen": ranks_seen, "rccl_version": rccl_version,
                        "cpus_per_rank": len(cpus) if cpus else None,
                        "launcher": "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else
