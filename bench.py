@@ -14,6 +14,11 @@ of configs[2]).  Inputs are resident in HBM before the timed region.  Frames sha
 collective (weak scaling); for N > 1 every step ends with the one RCCL all_gather of the padded detections
 (SURVEY.md 8e), packed behind the batch's NMS and enqueued on the pipeline's communication stream (no launch stream carries it).
 Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full adds what takes runs of
+its own after the timed steps: the per-kernel replay (`roofline`, `block_kernel`, `meta_kernel`, `kernel_ms_per_frame`), the
+Meta-Kernel + DLA backbone replay (`meta_dla_forward`) and the CPU baseline (`cpu_baseline`); without it those fields are null
+(`cpu_baseline` absent).
 """
 import argparse
 import json
@@ -304,7 +309,10 @@ def main(argv=None):
     ap.add_argument("--config", default="waymo", choices=["waymo", "kitti"],
                     help="waymo = rangedet_veh_wo_aug_4_18e on 64x2650(pad 2656)x8 (BASELINE configs[1]/[2], the metric's workload); "
                          "kitti = BASELINE configs[4]: 64x2048x5 range images, vehicle + pedestrian heads (named in config.workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the per-kernel and backbone replays (roofline figures) and the CPU baseline; "
+                         "a plain run reports the timed steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--frames", type=int, default=2, help="distinct synthetic batches cycled through")
     ap.add_argument("--inflight", type=int, default=3,
                     help="batches in flight per GPU (pipelines on separate streams).  3 since round 5: with the post-processing on each batch's own "
@@ -323,7 +331,7 @@ def main(argv=None):
                     help="diagnostic (rdlib.RD_WNMS_DIAG_NO_SKIP): the weighted NMS clips every pair the reference clips -- same results, for A/B and tests")
     ap.add_argument("--wnms-cap", type=int, default=8192, help="rows per frame the weighted NMS is sized for (checked every step)")
     ap.add_argument("--backbone-reps", type=int, default=10,
-                    help="replays of the Meta-Kernel + DLA backbone steps for the `meta_dla_forward` block (0: skip that block -- the rocprofv3 / PMC "
+                    help="with --full: replays of the Meta-Kernel + DLA backbone steps for the `meta_dla_forward` block (0: skip that block -- the rocprofv3 / PMC "
                          "passes of tools/profile_round.sh use 0 so that every profiled launch belongs to a full forward and the per-kernel averages "
                          "are those of the `roofline` block)")
     ap.add_argument("--repeats", type=int, default=1,
@@ -616,9 +624,9 @@ def main(argv=None):
         assert host[last]["step"] == total_steps - 1
         dumped = dump_outputs(args.dump_outputs, multi.pipes[last], host[last]["outs"])
 
-    # ---- per-kernel timing with HIP events on the launch stream, over a replay of the same steps ------------------
+    # ---- --full: per-kernel timing with HIP events on the launch stream, over a replay of the same steps ----------
     roof = meta_info = prof = backbone_info = block_info = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the forwards of the timed steps back to back on ONE stream with nothing else on the GPU, then the post-processing of those
         # batches the same way: every kernel runs alone at a steady clock, which is what a `rocprofv3 --kernel-trace --stats` pass
         # of `bench.py --inflight 1` reports (profiles/).  In the timed region two batches overlap on two launch streams plus the
@@ -772,9 +780,9 @@ def main(argv=None):
                 elapsed / (args.steps * world * Bf) * world,
                 (conv_bytes(pipe.plan, 2 if dt in rdlib.H16 else 4) + NPIX * 262) / 1e9,
                 (conv_flops(pipe.plan)[0] + META_FLOP_PER_PX * NPIX) / 1e9),
-            "kernel_ms_per_frame": {k: v[0] / max(1, min(args.steps, 20)) / Bf for k, v in prof.items()},
+            "kernel_ms_per_frame": {k: v[0] / max(1, min(args.steps, 20)) / Bf for k, v in prof.items()} if prof else None,
         }
-        if not args.no_cpu_baseline and world == 1 and not kitti:
+        if args.full and not args.no_cpu_baseline and world == 1 and not kitti:
             from oracle import input_ref   # (the checker's numpy transform: only this leg may touch oracle/)
             out["cpu_baseline"] = cpu_baseline(params, [input_ref.make_frame(i) for i in range(3)])
         line = json.dumps(out)

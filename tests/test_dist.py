@@ -272,6 +272,7 @@ def test_bench_rccl_gather_world1():
     nc = _json_line(ns.stdout)["config"]
     assert nc["results_sha256_last_step"] == pc["results_sha256_last_step"] and nc["wnms_kept"] == pc["wnms_kept"]
     for d in (p, g):                                                           # the spread fields of the report
+        assert d["roofline"] is None and d["meta_dla_forward"] is None and "cpu_baseline" not in d    # (a plain run: no --full replays)
         assert d["repeats"] == 2 and len(d["region_ms"]) == 2 and d["steps"] == 5
         assert d["ms_per_step_p5"] <= d["ms_per_step_p50"] <= d["ms_per_step_p95"]
         assert d["value_min"] <= d["value"] <= d["value_max"]
@@ -313,7 +314,7 @@ def test_bench_results_independent_of_block_fusion():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "RD_NO_FUSE_BLOCK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "3", "--repeats", "3", "--backbone-reps", "0",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     outs = []
     for extra in ({}, {"RD_NO_FUSE_BLOCK": "1", "RD_DEV_SWITCHES": "1"}):
         r = subprocess.run(cmd, env=dict(env, **extra), capture_output=True, text=True, timeout=900)
@@ -404,7 +405,8 @@ def test_bench_other_configurations_run(extra):
     on the headline workload, one batch in flight -- prints a well-formed line (the driver only ever runs the default)."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline",
+           "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)

@@ -37,7 +37,7 @@ if [ "$MODE" = steps ] || [ "$MODE" = both ]; then
 fi
 if [ "$MODE" = bench ] || [ "$MODE" = both ]; then
   for i in $(seq "$REPS"); do
-    echo "A [$A]  $(env $A timeout -s KILL 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | tee "$O/bench_A_$i.json" | python -c "$P")"
-    echo "B [$B]  $(env $B timeout -s KILL 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | tee "$O/bench_B_$i.json" | python -c "$P")"
+    echo "A [$A]  $(env $A timeout -s KILL 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | tee "$O/bench_A_$i.json" | python -c "$P")"
+    echo "B [$B]  $(env $B timeout -s KILL 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | tee "$O/bench_B_$i.json" | python -c "$P")"
   done | tee "$O/ab.txt"
 fi
