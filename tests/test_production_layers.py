@@ -12,7 +12,7 @@ mxnext/complicate.py:26-45), and the device output must agree PER ELEMENT to one
 (|got - ref| <= 2^-8 |ref| for bf16, 2^-11 for fp16, plus fp32 summation-order noise).  A fused BasicBlock (round 5,
 rd_block64_bn_act) must be BIT-IDENTICAL to the two launches it replaces, which are replayed on scratch buffers and checked per
 element like every other conv (conv2 on the device's own intermediate).  The Meta-Kernel step is checked
-against oracle/graph_ref.meta_kernel_unit (meta_kernel.py:166-240) with test_meta_kernel_unit's error model.
+against oracle/graph_ref.meta_kernel_unit (meta_kernel.py:166-240) with the per-element error model of tests/meta_model.py.
 """
 import time
 
@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import HIP_ONLY
+from meta_model import _meta_ref_and_sigma
 from oracle import graph_ref as G
 from oracle import input_ref as IR
 from rangedet_amd import lib as R
@@ -73,36 +74,6 @@ class _Host:
     def invalidate(self, ref):
         for key in [k for k in self.cache if k[0] == ref.buf]:
             del self.cache[key]
-
-
-def _meta_ref_and_sigma(data, coord, P, name, u):
-    """oracle/graph_ref.meta_kernel_unit (meta_kernel.py:166-240 + dla_backbone.py:92-97) for ONE image, restated here only to
-    also return the per-element standard deviation the 16-bit Meta-Kernel's roundings imply (u = half an ulp of the type):
-      h (32 hidden units) and s1*W1 are rounded            -> var(w_c)  = u^2/3 * 2 * sum_j (W1_cj h_j)^2
-      a = relu(s1 d w + t1) is rounded                      -> var(a)    = (s1 d)^2 var(w_c) + u^2/3 a^2
-      A (576 -> 64) is rounded                              -> var(pre)  = sum A^2 var(a) + u^2/3 sum (A a)^2
-      y = relu(s2 pre + t2)                                 -> sigma_y   = |s2| sqrt(var(pre))     (the output rounding is added by the caller)
-    The relative coordinates / the 3 -> 32 layer are fp32-accurate on the device (hi + lo split operands)."""
-    B, C, H, W = data.shape
-    pre_, Wn = name + "_", str(W)
-    T = G.T
-    cs = F.unfold(coord, 3, padding=1).view(B, 3, 9, H, W)
-    rel = (cs - coord.unsqueeze(2)).reshape(B, 3, 9 * H, W)
-    h = F.relu(F.conv2d(rel, T(P[pre_ + Wn + "_mlp0_weight"]), T(P[pre_ + Wn + "_mlp0_bias"])))
-    W1 = T(P[pre_ + Wn + "_mlp1_weight"])
-    wts = F.conv2d(h, W1, T(P[pre_ + Wn + "_mlp1_bias"])).view(B, 64, 9, H, W)
-    t1q = F.conv2d(h * h, W1 * W1).view(B, 64, 9, H, W)                  # sum_j (W1_cj h_j)^2
-    ds = F.unfold(data, 3, padding=1).view(B, C, 9, H, W)
-    s1, t1 = (torch.from_numpy(v) for v in bn_affine(P, name + "point_wise_mlp_bn1", G.EPS))
-    s2, t2 = (torch.from_numpy(v) for v in bn_affine(P, name + "aggregation_bn1", G.EPS))
-    a = F.relu((ds * wts).reshape(B, C * 9, H, W) * s1.view(1, -1, 1, 1) + t1.view(1, -1, 1, 1))
-    q = u * u / 3.0
-    var_a = (ds.reshape(B, C * 9, H, W) * s1.view(1, -1, 1, 1)) ** 2 * (2.0 * q) * t1q.reshape(B, C * 9, H, W) + 2.0 * q * a * a
-    A = T(P[name + "aggregation_conv1_weight"])
-    pre = F.conv2d(a, A)
-    var = F.conv2d(var_a, A * A)                                        # (the A-rounding term is the second q a^2 above)
-    y = F.relu(pre * s2.view(1, -1, 1, 1) + t2.view(1, -1, 1, 1))
-    return y, s2.abs().view(1, -1, 1, 1) * var.sqrt()
 
 
 def _check(name, got, ref, dt, report, extra_abs=0.0):
