@@ -7,7 +7,7 @@
 // 8 x 32 output tile and its rounded result is written straight into LDS in the halo-image layout conv2 reads.  Price: conv1 runs
 // on 12 instead of 8 pixel fragments per tile (+25 % of the block's MFMAs), and x is fetched with a 12 x 36 halo.
 //
-// Same machinery as conv3x3_stream_kernel<2, .., FPW 2, FC 1, WD> (8 x 32 tiles, two 4-wave workgroups per CU, LDS-DMA with counted
+// Same machinery as conv3x3_stream_kernel<2, .., C3_8x32> (8 x 32 tiles, two 4-wave workgroups per CU, LDS-DMA with counted
 // waits, one workgroup barrier per step placed mid-block, fragment reads interleaved 1:1 with the MFMAs); what differs:
 //   * a tile is FOUR units of 9 steps: U0 = conv1 chunk 0, U1 = conv1 chunk 1, U2 = conv2 chunk 0, U3 = conv2 chunk 1 (chunk = 32
 //     input channels); the weight-slab stream is the 36 slabs [conv1 image | conv2 image] per tile through one 6-deep ring;
@@ -19,7 +19,7 @@
 //     consecutive flat positions 32 f .. 32 f + 31 of the 10 x 36 grid of t (tap (dh, dw) = +36 dh + dw), so 12 fragments cover all
 //     340 needed positions (wave w: fragments 3 w .. 3 w + 2; positions in columns 34, 35 and past row 9 are computed and dropped).
 //     The 16-byte slots of a pixel are XOR-swizzled with (flat position >> 2) & 3 -- conflict-free for any alignment of a fragment;
-//   * t is stored with the 34-pixel pitch and the by-column swizzle of the wide tile (k_conv3.h C3Cfg<.., WD>), pixels outside the
+//   * t is stored with the 34-pixel pitch and the by-column swizzle of the wide tile (k_conv3.h C3Cfg<.., C3_8x32>), pixels outside the
 //     image as ZERO (conv2's zero padding -- not conv1 evaluated on padding), so conv2's addressing is the production kernel's;
 //   * the software pipeline is cut once per tile, after U1: t does not exist before every wave has written its part, so U1's last
 //     step pre-reads nothing and U2's first fragments are read after the intermediate write (the other workgroup of the CU runs

@@ -1,9 +1,11 @@
 // 3x3 / stride-1 / pad-1 bf16 convolution as a persistent, fully asynchronous MFMA pipeline (the bulk of the
 // RangeDet FLOPs: backbone BasicBlocks dla_backbone.py:18-56 and the head towers head/builder.py:221-240).
 //
-// One workgroup (4 waves, one per SIMD, up to 512 registers each) per CU walks a list of output tiles of
-// 8 rows x 62 columns x all Cout.  Wave w owns output rows 2w, 2w+1 of the tile: 4 pixel fragments (2 rows x 2 x 32 px)
-// x NCT channel fragments (32 ch) = 4*NCT accumulators of 32x32 (cout 128: all 256 accumulation registers).
+// A workgroup (4 waves, one per SIMD) walks a list of output tiles of 8 rows x all Cout; wave w owns output rows 2w, 2w+1.  The kernel
+// has two tile shapes (C3Tile / C3Cfg below), described here for the first:
+//   8 x 62, ONE workgroup per CU (up to 512 registers per wave): 4 pixel fragments per wave (2 rows x 2 x 32 px) x NCT channel
+//           fragments (32 ch) = 4*NCT accumulators of 32x32 (cout 128: all 256 accumulation registers);
+//   8 x 32, TWO workgroups per CU: 2 pixel fragments per wave (2 rows x 32 px), half the accumulators and half the LDS.
 //
 //   unit  = (tile, 32-channel k-chunk): one halo image 10 rows x 64 columns x 64 B = 40 KB in LDS, DOUBLE buffered:
 //           the halo of unit u+1 (possibly the next tile) is fetched by LDS-DMA while unit u is computed;
@@ -16,7 +18,7 @@
 //
 // All DMA traffic of a wave retires in order, so "my part of slab g+1 has landed" is a counted s_waitcnt vmcnt(N) with
 // N = DMA instructions issued after it -- a compile-time constant per tap because every step issues exactly IPW slab
-// instructions and every unit 10 halo instructions (dummy re-fetches keep that true at the end of the list).
+// instructions and every unit 10 (8 x 32: 6) halo instructions (dummy re-fetches keep that true at the end of the list).
 // LDS bytes per MFMA: (4 + NCT) KB / (4*NCT) = 0.5 KB (cout 128), 0.75 KB (cout 64) -- a quarter of ds_read_b128 peak.
 #pragma once
 #include "k_conv.h"
@@ -70,52 +72,44 @@ struct Conv3Args {
   const bf16_t* x2; int x2_cs, x2_co, nchunk1, nslots2; long x2_bs;
 };
 
-// Tile = 8 output rows x 62 columns (halo 10 x 64 pixels): wave w owns rows 2w, 2w+1, each as two 32-pixel fragments, so
-// pixel fragment i of a wave = row 2w + (i >> 1), columns 32*(i & 1) ..  (+2048 bytes per fragment in the halo image, as
-// a halo row is 64 pixels x 64 B = two fragments).  Against 4 x 126 tiles: 10/8 instead of 6/4 halo rows per output row
-// (less HBM and LDS-DMA traffic per pixel) and a finer column grid (2656 = 42.8 tiles of 62: 99.6 % of the computed
-// columns are real, 95.8 % with 126; 664: 97 % instead of 88 %; 166: 89 % instead of 66 %).
+// The two tile shapes.  Both are 8 output rows (halo 10 rows; wave w owns rows 2w, 2w+1) by all Cout, with two halo buffers: the halo
+// of unit u+1 is fetched while unit u is consumed.
 //
-// FPW = pixel fragments per wave.  FPW 4 is the tile above (one workgroup per CU, one wave per SIMD with the whole register
-// file).  FPW 2: tile = 4 rows x 62 columns (halo 6 x 64), wave w owns row w; half the accumulators (256 registers per wave)
-// and 75 KB of LDS, so TWO workgroups share a CU (two waves per SIMD): each is its own asynchronous pipeline with its own
-// barriers, and one's barrier waits, DMA-issue stalls and epilogue run under the other's MFMAs.  The price is 6/4 instead
-// of 10/8 halo rows per output row, so it is for the MFMA-bound 128-channel layers, not for the HBM-bound 64-channel ones.
+// C3_8x62: 62 output columns from a halo of 10 x 64 pixels; each row of a wave is two 32-pixel fragments, so pixel fragment i of a
+// wave = row 2w + (i >> 1), columns 32*(i & 1) ..  (+2048 bytes per fragment in the halo image, as a halo row is 64 pixels x 64 B =
+// two fragments).  One workgroup per CU, one wave per SIMD with the whole register file.  Against 4 x 126 tiles: 10/8 instead of
+// 6/4 halo rows per output row (less HBM and LDS-DMA traffic per pixel) and a finer column grid (2656 = 42.8 tiles of 62: 99.6 % of
+// the computed columns are real, 95.8 % with 126; 664: 97 % instead of 88 %; 166: 89 % instead of 66 %).
 //
-// FC = 32-pixel fragments per tile row (2: 62 output columns, halo 64; 1: 30 output columns, halo 32).  <FPW 2, FC 1> is the
-// 8-row x 30-column tile: wave w owns rows 2w, 2w+1 like the 8 x 62 tile (10/8 halo rows), half as wide, 72 KB of LDS, two
-// workgroups per CU -- the 4-row tile's stall hiding without its 6/4 halo rows, for the HBM-bound 64-channel layers.
-constexpr int C3_TW = 62;                  // output columns per tile (halo = 64 columns exactly), FC 2
-constexpr int C3_ROWB = 64 * 64;           // bytes of one halo row, FC 2
-// NHB = halo buffers (round 3).  2: the halo of unit u+1 is fetched while unit u is consumed.  3 (cout 64 on the 8 x 30 tiles
-// only -- the HBM-bound layers): the fetch runs TWO units ahead, so a piece has a whole unit (>= 9 steps) to arrive instead of
-// the 3 - 8 steps between its issue and the barrier of ordinal NS-2, and twice as many bytes are in flight per CU; the third
-// 20-KB buffer is paid for with a 5-deep instead of 8-deep weight ring and the (FOLD-unused) scale / shift array.
-// WD (round 3): the 8-row tile with ALL 32 columns of its one fragment per row live -- 8 x 32 outputs from a halo image of 10 rows
-// x 34 pixels (row pitch 34 pixels = 2 176 B instead of 32).  On the 8 x 30 tile two of every 32 MFMA columns compute pixels that
-// are thrown away (6.25 % of every conv's MFMAs, and the convs are MFMA / power bound); 2656 = 83 x 32 exactly.
-// The halo's 340 pixels are 21.25 one-KB pieces: 6 per wave (the last ones fetch the zero page), LDS = 2 x 24 KB + ring = 80 KB
-// exactly (no scale / shift array: FOLD only; cout 64 goes back to two halo buffers and its 8-deep ring).
-template <int NCT, int FPW = 4, int FC = 2, int NHB = 2, bool WD = false> struct C3Cfg {
-  static_assert(!WD || (FPW == 2 && FC == 1 && NHB == 2), "wide tile: 8 x 32, two halo buffers");
-  static constexpr int RW = FPW / FC;                    // output rows per wave
-  static constexpr int TH = 4 * RW;                      // output rows per tile (8 or 4)
-  static constexpr int COLS = WD ? 34 : 32 * FC;         // halo columns (= row pitch of the halo image in pixels)
-  static constexpr int TW = WD ? 32 : COLS - 2;          // output columns per tile
+// C3_8x32: ALL 32 columns of the one fragment per row live -- 8 x 32 outputs from a halo image of 10 rows x 34 pixels (row pitch
+// 34 pixels = 2 176 B); 2656 = 83 x 32 exactly.  Half the accumulators (256 registers per wave) and 80 KB of LDS exactly (2 x 24 KB of
+// halo + ring; no scale / shift array: FOLD only), so TWO workgroups share a CU (two waves per SIMD): each is its own asynchronous
+// pipeline with its own barriers, and one's barrier waits, DMA-issue stalls and epilogue run under the other's MFMAs.  The halo's 340
+// pixels are 21.25 one-KB pieces: 6 per wave (the last ones fetch the zero page).
+//
+// Tried and retired (profiles/EXPERIMENTS.md): a 4 x 62 two-workgroup tile paid 6/4 instead of 10/8 halo rows per
+// output row and lost to the 8-row two-workgroup tile on every layer class.  An 8 x 30 tile (halo pitch 32) threw away two of every
+// 32 MFMA columns -- 6.25 % of the MFMAs of convs that are MFMA / power bound -- and lost to 8 x 32.  A third halo
+// buffer (fetch two units ahead, cout 64 on 8 x 30) needed the LDS that the 34-pixel pitch now takes.
+enum C3Tile { C3_8x62 = 0, C3_8x32 = 1 };
+template <int NCT, C3Tile TILE = C3_8x62> struct C3Cfg {
+  static constexpr bool WIDE = TILE == C3_8x32;          // every MFMA column live, two workgroups per CU
+  static constexpr int RW = 2;                           // output rows per wave
+  static constexpr int FC = WIDE ? 1 : 2;                // 32-pixel fragments per tile row
+  static constexpr int FPW = RW * FC;                    // pixel fragments per wave
+  static constexpr int TH = 4 * RW;                      // output rows per tile
+  static constexpr int COLS = WIDE ? 34 : 64;            // halo columns (= row pitch of the halo image in pixels)
+  static constexpr int TW = WIDE ? 32 : 62;              // output columns per tile
   static constexpr int ROWB = COLS * 64;                 // bytes of one halo row
   static constexpr int HROWS = TH + 2;                   // halo rows
   static constexpr int NPX = HROWS * COLS;               // pixels of one halo image
-  static constexpr int HPW = WD ? (NPX + 63) / 64 : HROWS * ROWB / 4096;   // 1-KB halo pieces (16 pixels) per wave and unit
-  static constexpr int HALO = HPW * 4096;                // bytes of one halo buffer (WD: incl. the padding pieces)
-  static constexpr int HPC = WD ? 7 : HPW;               // schedule code of c3_halo_pieces
-  static_assert(NHB == 2 || (NHB == 3 && FPW == 2 && FC == 1 && NCT == 2), "three halo buffers: cout 64 on 8 x 30 tiles");
-  static constexpr int R = NHB == 3 ? 5 : FPW == 4 ? (NCT == 4 ? 7 : 10) : FC == 1 ? (NCT == 4 ? 4 : 8) : (NCT == 4 ? 3 : 6);   // ring depth (slabs)
+  static constexpr int HPW = (NPX + 63) / 64;            // 1-KB halo pieces (16 pixels) per wave and unit: 10 or 6
+  static constexpr int HALO = HPW * 4096;                // bytes of one halo buffer (8 x 32: incl. the padding pieces)
+  static constexpr int R = WIDE ? (NCT == 4 ? 4 : 8) : (NCT == 4 ? 7 : 10);   // ring depth (slabs)
   static constexpr int IPW = NCT / 2;                    // slab DMA instructions per wave per step
   static constexpr int SLAB = NCT * 2048;
-  static constexpr size_t LDS = (size_t)NHB * HALO + (size_t)R * SLAB + (NHB == 3 || WD ? 0 : 2 * NCT * 32 * sizeof(float));
+  static constexpr size_t LDS = 2 * (size_t)HALO + (size_t)R * SLAB + (WIDE ? 0 : 2 * NCT * 32 * sizeof(float));
 };
-constexpr int C3_TH = C3Cfg<4, 4>::TH;     // (the FPW 4 geometry, for code that sizes things before choosing a variant)
-constexpr int C3_HALO = C3Cfg<4, 4>::HALO;
 
 // packed bf16 conv-family weights: [32-ch chunk][tap][ks (2)][Cout/32][64 lanes][8 bf16], lane (mm, hi) of a fragment
 // holds W[co = 32*cb + conv_row_perm(mm)][ci = 32*chunk + 16*ks + 8*hi + j][tap].   get(co, ci, tap) -> float
@@ -215,29 +209,23 @@ constexpr int c3_nsteps(int TS) { return TS == 0 ? 9 : 6; }
 constexpr int c3_tap(int TS, int s) {            // tap index T = 3*(dh+1) + (dw+1) of step ordinal s
   return TS == 0 ? s : 3 * (s / 2) + (s % 2) + (TS == 2 ? 1 : 0);
 }
-// Halo pieces (C3_HPW = 10 per wave and unit) per step ordinal: 2 each at ordinals 0..4 of a 9-step unit; 4, 4, 2 at
-// ordinals 0..2 of a 6-step unit; the last ones are issued at least two steps before the wait that must cover them
-// (ordinal NS-2).
-// (HP = 6, the 4-row tile: 2 each at ordinals 0..2 of a 9-step unit, 3 each at ordinals 0..1 of a 6-step unit;
-//  HP = 5, the 8 x 30 tile: 1 each at ordinals 0..4 of a 9-step unit; 2, 2, 1 at ordinals 0..2 of a 6-step unit.)
-// (HP = 7 is the code of the wide 8 x 32 tile: 6 pieces, 2, 1, 1, 1, 1 at ordinals 0..4 of a 9-step unit; 2 each at 0..2 of a 6-step unit.)
-constexpr int c3_halo_last(int NS, int HP) { return HP == 7 ? (NS == 9 ? 4 : 2) : HP == 6 ? (NS == 9 ? 2 : 1) : (NS == 9 ? 4 : 2); }
-constexpr int c3_halo_pieces(int s, int NS, int HP) {
-  return HP == 7 ? (NS == 9 ? (s == 0 ? 2 : s <= 4 ? 1 : 0) : (s <= 2 ? 2 : 0))
-       : HP == 10 ? (NS == 9 ? (s <= 4 ? 2 : 0) : (s <= 1 ? 4 : (s == 2 ? 2 : 0)))
-       : HP == 6  ? (NS == 9 ? (s <= 2 ? 2 : 0) : (s <= 1 ? 3 : 0))
-                  : (NS == 9 ? (s <= 4 ? 1 : 0) : (s <= 1 ? 2 : (s == 2 ? 1 : 0)));
+// Halo pieces per step ordinal, all issued at least two steps before the wait that must cover them (ordinal NS-2).
+//   8 x 62 (10 per wave and unit): 2 each at ordinals 0..4 of a 9-step unit; 4, 4, 2 at ordinals 0..2 of a 6-step unit;
+//   8 x 32 (6 per wave and unit):  2, 1, 1, 1, 1 at ordinals 0..4 of a 9-step unit; 2 each at ordinals 0..2 of a 6-step unit.
+constexpr int c3_halo_last(int NS) { return NS == 9 ? 4 : 2; }   // ordinal of the last piece (either tile)
+constexpr int c3_halo_pieces(int s, int NS, C3Tile tile) {
+  return tile == C3_8x32 ? (NS == 9 ? (s == 0 ? 2 : s <= 4 ? 1 : 0) : (s <= 2 ? 2 : 0))
+                         : (NS == 9 ? (s <= 4 ? 2 : 0) : (s <= 1 ? 4 : (s == 2 ? 2 : 0)));
 }
-constexpr int c3_halo_first(int s, int NS, int HP) { int n = 0; for (int t = 0; t < s; ++t) n += c3_halo_pieces(t, NS, HP); return n; }
+constexpr int c3_halo_first(int s, int NS, C3Tile tile) { int n = 0; for (int t = 0; t < s; ++t) n += c3_halo_pieces(t, NS, tile); return n; }
 // DMA instructions a wave issues after "its part of slab g+2", as seen at the wait of step g (ordinal s of its unit):
 // the halo pieces of step g+2-R plus everything of steps g+3-R .. g-1.  Every step issues IPW slab instructions plus its
 // halo pieces.  At ordinal NS-2 the wait must also cover the last halo piece: the following step reads the next halo.
-// (NHB 3: the next unit's halo was issued during the PREVIOUS unit, i.e. before every slab this count skips -- no cap.)
-constexpr int c3_younger(int R, int IPW, int s, int NS, int HP, int NHB = 2) {
+constexpr int c3_younger(int R, int IPW, int s, int NS, C3Tile tile) {
   int n = (R - 3) * IPW;
-  for (int d = 1; d <= R - 2; ++d) n += c3_halo_pieces((((s - d) % NS) + NS) % NS, NS, HP);
-  const int cap = (NS - 3 - c3_halo_last(NS, HP)) * IPW;
-  if (NHB == 2 && s == NS - 2 && n > cap) n = cap;
+  for (int d = 1; d <= R - 2; ++d) n += c3_halo_pieces((((s - d) % NS) + NS) % NS, NS, tile);
+  const int cap = (NS - 3 - c3_halo_last(NS)) * IPW;
+  if (s == NS - 2 && n > cap) n = cap;
   return n;
 }
 // ---- tile bodies with units of DIFFERENT step counts (round 4, 8 x 32 tiles only) --------------------------------------------------
@@ -325,10 +313,7 @@ inline void pack_body_frag(int BODY, int cin, int cout, void* out, F get, int dt
 // pixel-pair view whose even / odd halves are whole 128-byte lines (x_cstride a multiple of 64, all of them convolved),
 // 2 = [64 channels | <= 16 channels] (rd_conv3x3_bn_act_cat), 3 = at most 16 input channels, 0 = homogeneous units.
 // RD_CONV_BODY=0 (dev switch, A/B): always 0.
-inline bool conv3_bodies_on() {
-  const DevSwitches& sw_ = dev_switches();
-  return sw_.conv_body && sw_.conv_wide && sw_.conv_w30 == 2 && sw_.conv_th4 == 1 && !sw_.conv_v1;
-}
+inline bool conv3_bodies_on() { return dev_switches().conv_body && !dev_switches().conv_v1; }
 inline int conv3_body_s2(int cin, int x_cstride, bool folded) { return folded && conv3_bodies_on() && x_cstride % 64 == 0 && cin == x_cstride ? 1 : 0; }
 inline int conv3_body_small(int cin, bool folded) { return folded && conv3_bodies_on() && cin <= 16 ? 3 : 0; }
 inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && conv3_bodies_on() && cin1 == 64 && cin2 <= 16 ? 2 : 0; }
@@ -357,24 +342,23 @@ inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && co
 // accumulators of 4 registers.  Block 0 = weight fragments 0..3, block 1 = 4..7, pixel-major inside a block, so a pixel half-fragment's
 // register is free after its 4th MFMA of block 1 and is re-read for the next step right there (single buffered); the barrier, the counted
 // waits and the DMA schedule are those of the 32 x 32 form (12 fragment reads per step in both).
-template <int NCT, int DBG = 0, int TS = 0, bool HEAD = false, bool SC = false, bool FOLD = false, int FPW = 4, int FC = 2, int NHB = 2,
-          int DT = RD_BF16, bool WD = false, bool GRP = false, int BODY = 0, bool M16 = false>
-__global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel(Conv3Args a) {
-  static_assert(!M16 || (NCT == 4 && FPW == 2 && FC == 1 && WD && FOLD && !SC && !GRP && TS == 0 && BODY == 0 && DBG == 0),
+template <int NCT, int DBG = 0, int TS = 0, bool HEAD = false, bool SC = false, bool FOLD = false, C3Tile TILE = C3_8x62,
+          int DT = RD_BF16, bool GRP = false, int BODY = 0, bool M16 = false>
+__global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream_kernel(Conv3Args a) {
+  using Cfg = C3Cfg<NCT, TILE>;
+  constexpr bool WD = Cfg::WIDE;                 // the 8 x 32 tile
+  constexpr int FPW = Cfg::FPW, FC = Cfg::FC;    // pixel fragments per wave (4 or 2), per tile row (2 or 1)
+  static_assert(!M16 || (NCT == 4 && WD && FOLD && !SC && !GRP && TS == 0 && BODY == 0 && DBG == 0),
                 "16 x 16 x 32 form: cout 128 on the 8 x 32 tiles, folded scales, all nine taps");
   static_assert(BODY == 0 || (WD && FOLD && !GRP && !HEAD && (TS == 0 || TS == 1)), "heterogeneous tile bodies: 8 x 32 tiles, folded scales");
-  static_assert(!GRP || (FOLD && !SC && !(HEAD && FPW == 4)), "two problems per launch: folded scales, no shortcut, output-conv weights from L2");
-  static_assert((NHB == 2 && !WD) || FOLD, "three halo buffers / wide tile: no room for the scale / shift array");
-  static_assert(!HEAD || (NCT == 4 && TS == 0 && (FPW == 4 || FC == 1)), "fused output conv: cout 128, all nine taps, 8-row tiles");
+  static_assert(!GRP || (WD && FOLD && !SC), "two problems per launch: 8 x 32 tiles (output-conv weights from L2), folded scales, no shortcut");
+  static_assert(!WD || FOLD, "8 x 32 tile: no room for the scale / shift array");
+  static_assert(!HEAD || (NCT == 4 && TS == 0), "fused output conv: cout 128, all nine taps");
   constexpr bool PH = TS == 3;                   // all phases of a transposed conv: (tile, phase) list, run-time tap-set side
   static_assert(!PH || (FOLD && !SC && !HEAD && !GRP), "all-phase transposed conv: folded scales, no shortcut / output conv / second problem");
   static_assert(!(HEAD && SC), "a head tower has no shortcut");
-  static_assert(FPW == 4 || FPW == 2, "4 or 2 pixel fragments per wave");
-  static_assert(FC == 2 || (FC == 1 && FPW == 2), "30-column tiles: two fragments per wave");
-  using Cfg = C3Cfg<NCT, FPW, FC, NHB, WD>;
-  constexpr int HPC = Cfg::HPC;
   constexpr int R = Cfg::R, IPW = Cfg::IPW, SLAB = Cfg::SLAB, COUT = NCT * 32;
-  constexpr int C3_HALO = Cfg::HALO, C3_HPW = Cfg::HPW, C3_TH = Cfg::TH;   // (shadow the FPW 4 file-scope constants)
+  constexpr int C3_HALO = Cfg::HALO, C3_HPW = Cfg::HPW, C3_TH = Cfg::TH;
   constexpr int C3_TW = Cfg::TW, C3_ROWB = Cfg::ROWB, RW = Cfg::RW;
   constexpr int NR = FPW + NCT;                  // fragment reads per k-step
   constexpr int NM = FPW * NCT;                  // MFMAs per k-step
@@ -384,13 +368,11 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
   HIP_DYNAMIC_SHARED(unsigned char, smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 31, hi = lane >> 5;
-  constexpr int RING = NHB * C3_HALO;
-  // byte offset of the halo buffer after / before buffer a in the cycle
-  auto hnext = [](int a_) { return NHB == 2 ? C3_HALO - a_ : (a_ == (NHB - 1) * C3_HALO ? 0 : a_ + C3_HALO); };
-  auto hprev = [](int a_) { return NHB == 2 ? C3_HALO - a_ : (a_ == 0 ? (NHB - 1) * C3_HALO : a_ - C3_HALO); };
+  constexpr int RING = 2 * C3_HALO;
+  auto hflip = [](int a_) { return C3_HALO - a_; };   // byte offset of the other halo buffer
   float* Sc = (float*)(smem + RING + R * SLAB);
   constexpr int HWOFF = RING + R * SLAB + 2 * COUT * (int)sizeof(float);   // HEAD: 16 KB of packed output-conv weights
-  if (NHB == 2 && !WD && tid < COUT) {
+  if (!WD && tid < COUT) {
     Sc[tid] = a.scale ? a.scale[tid] : 1.f;
     Sc[COUT + tid] = a.shift ? a.shift[tid] : 0.f;
   }
@@ -554,7 +536,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       ok = hsp < hns && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim && pp < Cfg::NPX && !(DBG & 16);
       src = hbase + (long)((r * a.W + cc) * hpxb + hsp * 16);
     } else {
-    const int r = q / (2 * FC), c16 = (q % (2 * FC)) * 16;
+    const int r = q >> 2, c16 = (q & 3) * 16;
     const int cc = c16 + l4;
     ok = hsok && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim && !(DBG & 16);
     const unsigned char* sp = hbase + ((long)r * a.W + c16) * (long)a.x_cs * 2;
@@ -674,12 +656,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
   halo_begin();
 #pragma unroll
   for (int j = 0; j < C3_HPW; ++j) halo_piece(0, j);
-  if constexpr (NHB == 3) {   // the fetch runs two units ahead: unit 1 as well
-    halo_begin();
-#pragma unroll
-    for (int j = 0; j < C3_HPW; ++j) halo_piece(C3_HALO, j);
-  }
-  if constexpr (HEAD && FPW == 4) {   // (FPW 2: no LDS to spare for them with two workgroups per CU -- read from L2 in the epilogue)
+  if constexpr (HEAD && !WD) {   // (8 x 32: no LDS to spare for them with two workgroups per CU -- read from L2 in the epilogue)
 #pragma unroll
     for (int j = 0; j < 4; ++j) dma_s(a.hw + (wave * 4 + j) * 1024, lane * 16, HWOFF + (wave * 4 + j) * 1024);
   }
@@ -716,13 +693,13 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
   {                                                                                                                  \
     constexpr int T_ = c3_tap(TS, (S)), TN_ = c3_tap(TS, ((S) + 1) % NS);                                            \
     constexpr int dh_ = T_ / 3, dw_ = T_ % 3, ndh_ = TN_ / 3, ndw_ = TN_ % 3;                                        \
-    constexpr int NH_ = c3_halo_pieces((S), NS, HPC), NP_ = IPW + NH_;   /* DMA pieces of this step */                    \
+    constexpr int NH_ = c3_halo_pieces((S), NS, TILE), NP_ = IPW + NH_;   /* DMA pieces of this step */                    \
     const int acur_ = (C3_AO(dw_) + abuf + dh_ * C3_ROWB) ^ 32;                                                        \
     const int bcur_ = boff + rslot * SLAB;                                                                           \
     const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = ((S) == NS - 1 && PH && lastc ? pq0 : C3_AO(ndw_)) + ((S) == NS - 1 ? hnext(abuf) : abuf) + ndh_ * C3_ROWB; \
+    const int anext_ = ((S) == NS - 1 && PH && lastc ? pq0 : C3_AO(ndw_)) + ((S) == NS - 1 ? hflip(abuf) : abuf) + ndh_ * C3_ROWB; \
     const int bnext_ = boff + rnext_ * SLAB;                                                                         \
-    const int hbuf_ = hprev(abuf);   /* NHB 2: the other buffer (unit u+1); NHB 3: unit u-1's, for unit u+2 */       \
+    const int hbuf_ = hflip(abuf);   /* the other buffer: unit u+1 */                                                 \
     C3_FENCE();                                                                                                      \
     _Pragma("unroll") for (int n = 0; n < NM; ++n) {                                                                 \
       MM0(0, n)                                                                                                      \
@@ -733,14 +710,14 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       if (n < NR) C3_RD(0, n, anext_, bnext_, 0)                                                                     \
     }                                                                                                                \
     if (NR > NM / 2) { _Pragma("unroll") for (int n = NM / 2; n < NR; ++n) C3_RD(0, n, anext_, bnext_, 0) }          \
-    C3_SYNC(c3_younger(R, IPW, (S), NS, HPC, NHB), NR)                                                            \
+    C3_SYNC(c3_younger(R, IPW, (S), NS, TILE), NR)                                                            \
     if ((S) == 0) halo_begin();                                                                                      \
     _Pragma("unroll") for (int n = NM / 2; n < NM; ++n) {                                                            \
       C3_MM(1, n)                                                                                                    \
       if (!(DBG & 4)) {   /* the step's DMA pieces, spread over the MFMA slots of this half block (slab pieces first) */ \
         _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                              \
           if (p * (NM / 2) / NP_ == n - NM / 2) {                                                                    \
-            if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, HPC) + p - IPW);                    \
+            if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                    \
             C3_FENCE();                                                                                              \
           }                                                                                                          \
       }                                                                                                              \
@@ -755,12 +732,12 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
 #define C3_STEP16(S)                                                                                                 \
   {                                                                                                                  \
     constexpr int TN_ = c3_tap(TS, ((S) + 1) % NS), ndh_ = TN_ / 3, ndw_ = TN_ % 3;                                  \
-    constexpr int NH_ = c3_halo_pieces((S), NS, HPC), NP_ = IPW + NH_;                                               \
+    constexpr int NH_ = c3_halo_pieces((S), NS, TILE), NP_ = IPW + NH_;                                               \
     const int bcur_ = boff + rslot * SLAB;                                                                           \
     const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = aoff[ndw_] + ((S) == NS - 1 ? hnext(abuf) : abuf) + ndh_ * C3_ROWB;                           \
+    const int anext_ = aoff[ndw_] + ((S) == NS - 1 ? hflip(abuf) : abuf) + ndh_ * C3_ROWB;                           \
     const int bnext_ = boff + rnext_ * SLAB;                                                                         \
-    const int hbuf_ = hprev(abuf);                                                                                   \
+    const int hbuf_ = hflip(abuf);                                                                                   \
     C3_FENCE();                                                                                                      \
     _Pragma("unroll") for (int n = 0; n < 16; ++n) {                                                                 \
       C3_MM16(0, n)                                                                                                  \
@@ -772,13 +749,13 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       if (n == 3) C3_RDP16(0, anext_)                                                                                \
       if (n == 7) C3_RDP16(1, anext_)                                                                                \
     }                                                                                                                \
-    C3_SYNC(c3_younger(R, IPW, (S), NS, HPC, NHB), 6)                                                                \
+    C3_SYNC(c3_younger(R, IPW, (S), NS, TILE), 6)                                                                \
     if ((S) == 0) halo_begin();                                                                                      \
     _Pragma("unroll") for (int n = 8; n < 16; ++n) {                                                                 \
       C3_MM16(1, n)                                                                                                  \
       _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                                \
         if (p * 8 / NP_ == n - 8) {                                                                                  \
-          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, HPC) + p - IPW);                 \
+          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                 \
           C3_FENCE();                                                                                                \
         }                                                                                                            \
       if (n == 11) C3_RDP16(2, anext_)                                                                               \
@@ -800,9 +777,9 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
     const int acur_ = (aoff[k1_.dw] + abuf + k1_.dh * C3_ROWB) ^ (k1_.slot << 5);                                    \
     const int bcur_ = boff + rslot * SLAB;                                                                           \
     const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = (aoff[kn_.dw] + (lastS_ ? hnext(abuf) : abuf) + kn_.dh * C3_ROWB) ^ (kn_.slot << 5);          \
+    const int anext_ = (aoff[kn_.dw] + (lastS_ ? hflip(abuf) : abuf) + kn_.dh * C3_ROWB) ^ (kn_.slot << 5);          \
     const int bnext_ = boff + rnext_ * SLAB;                                                                         \
-    const int hbuf_ = hprev(abuf);                                                                                   \
+    const int hbuf_ = hflip(abuf);                                                                                   \
     C3_FENCE();                                                                                                      \
     _Pragma("unroll") for (int n = 0; n < NM; ++n) {                                                                 \
       MM0(0, n)                                                                                                      \
@@ -825,7 +802,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
     }                                                                                                                \
     slab_advance();                                                                                                  \
     rslot = rnext_;                                                                                                  \
-    if (lastS_) abuf = hnext(abuf);                                                                                  \
+    if (lastS_) abuf = hflip(abuf);                                                                                  \
   }
   // (fragment read with an address that already carries the k-step's slot bit: C3_RD adds nothing for the pixel operand)
 #define C3_RDX(BUF, K, AADDR, BADDR, KS) C3_RD(BUF, K, AADDR, BADDR, KS)
@@ -866,7 +843,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
 #pragma unroll 1
       for (int c = 0; c < a.nchunk; ++c) {
         C3_STEP16(0) C3_STEP16(1) C3_STEP16(2) C3_STEP16(3) C3_STEP16(4) C3_STEP16(5) C3_STEP16(6) C3_STEP16(7) C3_STEP16(8)
-        abuf = hnext(abuf);
+        abuf = hflip(abuf);
       }
     } else {
     {   // first chunk of the tile, peeled: its first k-step starts the accumulators from C = 0 (FOLD: from the shift)
@@ -897,7 +874,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       if constexpr (BODY != 0) { C3_GBODY_FROM1(C3_MM) } else {
       C3_STEP(1) C3_STEP(2) C3_STEP(3) C3_STEP(4) C3_STEP(5)
       if constexpr (NS == 9) { C3_STEP(6) C3_STEP(7) C3_STEP(8) }
-      abuf = hnext(abuf);
+      abuf = hflip(abuf);
       }
     }
     if constexpr (BODY != 0) {
@@ -909,7 +886,7 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       if constexpr (PH) lastc = c == a.nchunk - 1;
       C3_STEP(0) C3_STEP(1) C3_STEP(2) C3_STEP(3) C3_STEP(4) C3_STEP(5)
       if constexpr (NS == 9) { C3_STEP(6) C3_STEP(7) C3_STEP(8) }
-      abuf = hnext(abuf);
+      abuf = hflip(abuf);
     }
     }
     }   // !M16
@@ -942,12 +919,12 @@ __global__ __launch_bounds__(256, (FPW == 2 ? 2 : 1)) void conv3x3_stream_kernel
       em = el & 31; ehi = el >> 5;
     } else
     asm volatile("" : "+v"(em), "+v"(ehi), "+v"(el));
-    // The transpose scratch of a wave is a quarter of the free halo buffer: 10 KB (FPW 4) or 6 KB (FPW 2).  A fragment's 32
-    // pixels x CW channels x 2 B must fit: all COUT channels in one pass, or (cout 128 on the 4-row tile) two passes of 64.
+    // The transpose scratch of a wave is a quarter of the free halo buffer: 10 KB (8 x 62) or 6 KB (8 x 32).  A fragment's 32
+    // pixels x CW channels x 2 B must fit: all COUT channels in one pass, or (cout 128 on the 8 x 32 tile) two passes of 64.
     constexpr int JW = (32 * COUT * 2 <= C3_HALO / 4) ? NCT : NCT / 2, CW = JW * 32, NPASS = NCT / JW;
-    static_assert(32 * CW * 2 <= C3_HALO / 4 && (!HEAD || NPASS == 1 || FPW == 2), "transpose scratch");
+    static_assert(32 * CW * 2 <= C3_HALO / 4, "transpose scratch");
     constexpr int ROWB = CW * 2, SPR = CW / 8, RPI = 64 / SPR;   // row bytes, 16-B slots per row, rows per store instr
-    unsigned char* scr = smem + hprev(abuf) + wave * (C3_HALO / 4);   // (the buffer of the unit just consumed)
+    unsigned char* scr = smem + hflip(abuf) + wave * (C3_HALO / 4);   // (the buffer of the unit just consumed)
     bf16_t* __restrict__ yrow0 = a.y + (eg ? a.g_y : 0) + (size_t)b * a.y_bs + (size_t)oh0 * a.Wo * a.y_cs + a.y_co + (PH ? e_ph * a.y_pc : 0);
     // (base of image b, not of the wave's first row: rows past the image bottom must not even form an address beyond the buffer)
     const bf16_t* __restrict__ rimg0 = a.res + (eg ? a.g_res : 0) + (size_t)b * a.r_bs + a.r_co + (PH ? e_ph * a.r_pc : 0);
@@ -1312,12 +1289,12 @@ inline int conv_num_cus() {
 }
 
 // One launch of one instantiation; the first launch of each raises its dynamic-LDS limit (once per process and instantiation).
-template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, int FPW, int FC, int NHB, int DT, bool WD = false, bool GRP = false, int BODY = 0, bool M16 = false>
+template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, C3Tile TILE, int DT, bool GRP = false, int BODY = 0, bool M16 = false>
 inline int c3_go(int grid, hipStream_t st, const Conv3Args& a) {
-  auto k = conv3x3_stream_kernel<NCT, 0, TS, HEAD, SC, FOLD, FPW, FC, NHB, DT, WD, GRP, BODY, M16>;
+  auto k = conv3x3_stream_kernel<NCT, 0, TS, HEAD, SC, FOLD, TILE, DT, GRP, BODY, M16>;
   static std::atomic<unsigned long long> seen{0};
   once_per_device(seen, [&] { allow_big_lds(k); });
-  constexpr size_t lds = C3Cfg<NCT, FPW, FC, NHB, WD>::LDS + (HEAD && FPW == 4 ? 16384 : 0);   // (8 x 62 tile: the output conv's weights in LDS)
+  constexpr size_t lds = C3Cfg<NCT, TILE>::LDS + (HEAD && TILE == C3_8x62 ? 16384 : 0);   // (8 x 62 tile: the output conv's weights in LDS)
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, a);
   return check_launch("conv3x3_stream_kernel");
 }
@@ -1353,22 +1330,13 @@ struct Conv3Phases { int nph, ts_mask, y_pc, r_pc; long w_pb; };
 // (a multiple of 32) channels come from x
 struct Conv3Src2 { const void* x; int cs, co, cin1, cin2; };
 inline bool conv3_phases_eligible(int cout, int flags) {
-  const DevSwitches& sw_ = dev_switches();
-  return (cout == 64 || cout == 128) && (flags & RD_SCALE_FOLDED) && sw_.conv_w30 && sw_.conv_wide && !sw_.conv_v1 &&
-         ((cout == 64 && sw_.conv_th4 != 3) || (cout == 128 && sw_.conv_th4 && sw_.conv_w30 == 2));
+  return (cout == 64 || cout == 128) && (flags & RD_SCALE_FOLDED) && !dev_switches().conv_v1;
 }
 // Does the launcher have the v_mfma_f32_16x16x32 form (RD_MFMA16) for this conv?  The packer side of the contract: an image made by
 // rd_pack_conv3x3_m16_host may only be launched where this says yes (the launch fails loudly otherwise).
-inline bool conv3_mfma16_ok(int cin, int cout, int stride_w, int W, bool headfuse) {
-  const DevSwitches& sw_ = dev_switches();
-  const bool head30_ok = sw_.conv_w30 == 2 && sw_.conv_head30 != 0;
-  return cout == 128 && stride_w == 1 && cin >= 32 && cin % 32 == 0 && !sw_.conv_v1 && sw_.conv_wide && sw_.conv_w30 == 2 && sw_.conv_th4 &&
-         (sw_.conv_th4 != 2 || W >= 600) && (!headfuse || head30_ok);
-}
-inline bool conv3_pair_eligible(int cout, int flags, int W, bool headfuse = false) {
-  const DevSwitches& sw_ = dev_switches();
-  return cout == 128 && (flags & RD_SCALE_FOLDED) && sw_.conv_th4 && sw_.conv_w30 == 2 && sw_.conv_wide && (sw_.conv_th4 != 2 || W >= 600) &&
-         (!headfuse || sw_.conv_head30 != 0);   // (RD_CONV_HEAD30=0: no fused output conv on the two-workgroup tiles -> two launches)
+// (with or without a fused output conv, at any width: an RD_MFMA16 launch always takes the 8 x 32 tile)
+inline bool conv3_mfma16_ok(int cin, int cout, int stride_w) {
+  return cout == 128 && stride_w == 1 && cin >= 32 && cin % 32 == 0 && !dev_switches().conv_v1;
 }
 
 template <int DT>
@@ -1409,32 +1377,22 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
   // zero bytes for padding: the tail every packer appends to the weight image (k_conv.h RD_CONV_TAIL)
   a.zero16 = (const unsigned char*)w + conv_packed_body_bytes(c3_nsteps(ts), cin, cout, RD_BF16);
   a.H = H; a.W = W; a.B = B; a.nslots = cin_slots(cin, RD_BF16); a.nchunk = (cin + 31) / 32; a.flags = flags;   // (without RD_SCALE_FOLDED)
-  // Two workgroups per CU (FPW 2) for every layer with folded scale and no fused output conv, on 8-row x 30-column tiles
-  // (FC 1).  Measured A/B, frames/s end to end: 4 x 62 tiles for the cout-128 layers +2.5 % over 8 x 62 everywhere (W = 332
-  // layers 70 -> 53 us, W = 1328 head convs 200 -> 179 us); 8 x 30 for the cout-64 layers +0.7 % on top (the HBM-bound
-  // layers keep their 10/8 halo rows); 8 x 30 instead of 4 x 62 for the cout-128 layers another +1.4 % (14 % fewer halo
-  // pieces per pixel, ring depth 4 instead of 3).  Dev switches: RD_CONV_TH4=0 -> cout 128 on 8 x 62, =3 -> cout 64 on
-  // 4 x 62 too; RD_CONV_W30=0 -> no 8 x 30 tiles, =1 -> only for cout 64.
-  const DevSwitches& sw_ = dev_switches();
-  const int th4_mode = sw_.conv_th4, head30 = sw_.conv_head30, w30_mode = sw_.conv_w30;
-  const bool hb3 = sw_.conv_hb3 != 0;   // cout 64 on the 8 x 30 tiles: halo fetch two units ahead (three buffers)
+  // Tile.  Two workgroups per CU on 8 x 32 tiles for every layer with folded scales and no fused output conv.  Measured A/B,
+  // frames/s end to end, against 8 x 62 everywhere: +2.5 % from two workgroups per CU on the cout-128 layers (W = 332 layers
+  // 70 -> 53 us, W = 1328 head convs 200 -> 179 us), +0.7 % more from the cout-64 layers, +1.4 % more from 8-row instead of 4-row
+  // two-workgroup tiles (14 % fewer halo pieces per pixel, ring depth 4 instead of 3), then every MFMA column live (8 x 32 for 8 x 30).
+  // With a fused output conv on that tile the conv's 16 KB of weights no longer fit in LDS and are re-read from L2 per fragment and
+  // pass; measured per layer: W = 1328 213 -> 205 us, W = 664 109 -> 107 us, W = 2656 398 -> 405 us, so the full-width level stays
+  // on the 8 x 62 tile -- unless it is in the 16 x 16 x 32 form, where the two-workgroup tile wins at full width too (W 2656:
+  // 352 -> 328 us, +0.5 % frames/s on one box, profiles/EXPERIMENTS.md), or a two-problem launch, whose output-conv weights are per
+  // problem and come from L2.  Un-folded scales (stand-alone use of the C ABI) need the scale / shift array in LDS: 8 x 62.
   const bool headfuse = head && !sc;
-  // (fused output conv on the two-workgroup tiles: its 16 KB of weights no longer fit in LDS and are re-read from L2 per
-  //  fragment and pass; measured per layer: W = 1328 213 -> 205 us, W = 664 109 -> 107 us, W = 2656 398 -> 405 us, so the
-  //  full-width level stays on the 8 x 62 tile.  RD_CONV_HEAD30=0 -> never, =2 -> always)
-  // (a two-problem launch always takes the two-workgroup tile: its output-conv weights are per problem and come from L2)
-  // (round 6: in the 16 x 16 x 32 form the two-workgroup tile wins at full width too -- W 2656: 352 -> 328 us, +0.5 % frames/s on one box,
-  //  profiles/EXPERIMENTS.md -- so an RD_MFMA16 image always takes it)
-  const bool head30_ok = w30_mode == 2 && (head30 == 2 || (head30 == 1 && (W <= 1400 || body == C3_BODY_M16)) || (g1 && head30));   // (only exists on the 8 x 30 tiles)
-  const bool th4 = th4_mode && (cout == 128 || th4_mode == 3) && fold && (!headfuse || head30_ok) && (th4_mode != 2 || W >= 600);
-  const bool w30_128 = w30_mode == 2 && th4 && cout == 128;
-  const bool w30 = w30_mode && fold && ((!th4 && cout == 64 && !headfuse) || w30_128);
-  RD_REQUIRE(!headfuse || !th4 || w30, RD_EINVAL, "conv3 + output conv: two workgroups per CU only on the 8 x 30 tiles");
-  const bool wd = sw_.conv_wide && w30;   // 8 x 32 tiles (34-pixel halo pitch) instead of 8 x 30: no discarded MFMA columns
-  const int th = th4 && !w30 ? 4 : C3_TH, tw = wd ? 32 : w30 ? C3Cfg<2, 2, 1>::TW : C3_TW;
+  RD_REQUIRE(!headfuse || cout == 128, RD_ESHAPE, "conv3 + output conv: cout %d (128)", cout);
+  const bool wide = fold && (!headfuse || W <= 1400 || body == C3_BODY_M16 || g1);
+  const int tw = wide ? C3Cfg<4, C3_8x32>::TW : C3Cfg<4, C3_8x62>::TW, th = C3Cfg<4>::TH;
   a.ncol = (W + tw - 1) / tw; a.nrow = (H + th - 1) / th; a.ntiles = a.ncol * a.nrow * B * a.ngrp;
   if (g1) {
-    RD_REQUIRE(wd && fold && !sc && ts == 0 && cout == 128 && sw == 1, RD_ESHAPE,
+    RD_REQUIRE(wide && fold && !sc && ts == 0 && cout == 128 && sw == 1, RD_ESHAPE,
                "conv3: two problems per launch need the 8 x 32 tile form (cout 128, folded scales, stride 1, no shortcut)");
     RD_REQUIRE(!headfuse == !g1->hw && !res == !g1->res && !shift == !g1->shift, RD_EINVAL,
                "conv3: the two problems of a launch must have the same structure (output conv / residual / shift)");
@@ -1449,117 +1407,99 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
     }
   }
   if (s2) {   // conv over [x | x2]: cin = cin1 + cin2, the first cin1 (full 32-channel chunks) from x
-    RD_REQUIRE(wd && !g1 && sw == 1 && s2->cin1 > 0 && s2->cin1 % 32 == 0 && s2->cin1 + s2->cin2 == cin && s2->cin2 > 0, RD_ESHAPE,
+    RD_REQUIRE(wide && !g1 && sw == 1 && s2->cin1 > 0 && s2->cin1 % 32 == 0 && s2->cin1 + s2->cin2 == cin && s2->cin2 > 0, RD_ESHAPE,
                "conv3: a two-tensor input needs the 8 x 32 tile form and cin1 a multiple of 32 (cin1 %d, cin2 %d, cin %d)", s2->cin1, s2->cin2, cin);
     a.x2 = (const bf16_t*)s2->x; a.x2_cs = s2->cs; a.x2_co = s2->co; a.x2_bs = (long)H * W * s2->cs;
     a.nchunk1 = s2->cin1 / 32; a.nslots2 = cin_slots(s2->cin2, RD_BF16); a.nslots = a.nchunk1 * 4;
   }
-  const int grid = std::min(a.ntiles, conv_num_cus() * (th4 || w30 ? 2 : 1));
-  a.xcd = sw_.conv_xcd && !g1 && (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
+  const int grid = std::min(a.ntiles, conv_num_cus() * (wide ? 2 : 1));
+  a.xcd = dev_switches().conv_xcd && !g1 && (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
   if (conv_trace_buf() && (size_t)grid * 8 <= (1u << 20)) a.trace = conv_trace_buf();
   ProfScope ps(RD_PROF_CONV3, st);
-#ifdef RD_CONV3_DEV   // ablation variants (DBG bits: 2 no barrier, 4 no DMA after the prologue, 16 halo from the zero page, 32 no vmcnt wait)
+#ifdef RD_CONV3_DEV   // ablation variants (bf16; DBG bits: 2 no barrier, 4 no DMA after the prologue, 16 halo from the zero page, 32 no vmcnt wait)
   static const int dbg = getenv("RD_CONV3_DBG") ? atoi(getenv("RD_CONV3_DBG")) : 0;
-#define C3_DBG_CASE(D) if (cout == 128 && dbg == D) { (void)hipFuncSetAttribute((const void*)conv3x3_stream_kernel<4, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); hipLaunchKernelGGL((conv3x3_stream_kernel<4, D>), dim3(grid), dim3(256), C3Cfg<4>::LDS, st, a); return check_launch("conv3x3_stream_kernel"); }
+  // plain cout-128 conv with un-folded scales on the 8 x 62 tile
+#define C3_DBG_CASE(D) if (cout == 128 && !fold && !head && ts == 0 && DT == RD_BF16 && dbg == D) { auto k = conv3x3_stream_kernel<4, D>; allow_big_lds(k); hipLaunchKernelGGL(k, dim3(grid), dim3(256), C3Cfg<4>::LDS, st, a); return check_launch("conv3x3_stream_kernel<dbg>"); }
   C3_DBG_CASE(2) C3_DBG_CASE(4) C3_DBG_CASE(16) C3_DBG_CASE(32)
 #undef C3_DBG_CASE
-  // cout 64 on the 8 x 30 tiles (plain 3x3, folded scales): 16 halo from the zero page, 64 residual from one L2-resident pixel,
-  // 128 no residual load, 4 no DMA after the prologue, 8 no MFMAs, 256 halo from the first MB of x (L2-resident REAL data), 1 no stores
-#define C3_DBG64(D)                                                                                                     \
-  if (cout == 64 && w30 && !sc && ts == 0 && dbg == D) {                                                                \
-    if (hb3) { auto k = conv3x3_stream_kernel<2, D, 0, false, false, true, 2, 1, 3>; allow_big_lds(k);                  \
-               hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<2, 2, 1, 3>::LDS), st, a); }                         \
-    else { auto k = conv3x3_stream_kernel<2, D, 0, false, false, true, 2, 1, 2>; allow_big_lds(k);                      \
-           hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<2, 2, 1, 2>::LDS), st, a); }                             \
+  // plain conv with folded scales on the 8 x 32 tile, cout 32 * N: (also) 8 no MFMAs, 64 residual from one L2-resident pixel, 128 no residual
+  // load, 256 halo from the first MB of x (L2-resident REAL data), 1 no stores
+#define C3_DBG(N, D)                                                                                                    \
+  if (cout == 32 * N && wide && !head && !g1 && !ph && !s2 && !body && sw == 1 && ts == 0 && DT == RD_BF16 && dbg == D) { \
+    auto k = conv3x3_stream_kernel<N, D, 0, false, false, true, C3_8x32>; allow_big_lds(k);                             \
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<N, C3_8x32>::LDS), st, a);                                      \
     return check_launch("conv3x3_stream_kernel<dbg>");                                                                  \
   }
-  C3_DBG64(4) C3_DBG64(8) C3_DBG64(16) C3_DBG64(64) C3_DBG64(128) C3_DBG64(256) C3_DBG64(257)
-#undef C3_DBG64
-#define C3_DBG128(D)                                                                                                    \
-  if (cout == 128 && w30 && !sc && !headfuse && ts == 0 && dbg == D) {                                                  \
-    auto k = conv3x3_stream_kernel<4, D, 0, false, false, true, 2, 1, 2>; allow_big_lds(k);                             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<4, 2, 1, 2>::LDS), st, a);                                      \
-    return check_launch("conv3x3_stream_kernel<dbg>");                                                                  \
-  }
-  C3_DBG128(4) C3_DBG128(8) C3_DBG128(16) C3_DBG128(2) C3_DBG128(32) C3_DBG128(256) C3_DBG128(257)
-#undef C3_DBG128
+  C3_DBG(2, 4) C3_DBG(2, 8) C3_DBG(2, 16) C3_DBG(2, 64) C3_DBG(2, 128) C3_DBG(2, 256) C3_DBG(2, 257)
+  C3_DBG(4, 4) C3_DBG(4, 8) C3_DBG(4, 16) C3_DBG(4, 2) C3_DBG(4, 32) C3_DBG(4, 256) C3_DBG(4, 257)
+#undef C3_DBG
 #endif
 #ifdef RD_CONV3_DEV_M16_ONLY   // tools/micro/conv16_dev.hip: only the plain cout-128 form on the 8 x 32 tiles, in its two MFMA shapes (a one-minute build)
-  RD_REQUIRE(wd && fold && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && DT == RD_BF16 && (!headfuse || body == C3_BODY_M16), RD_ESHAPE, "conv16_dev: plain bf16 cout-128 form only");
-  if (body == C3_BODY_M16 && headfuse) return c3_go<4, 0, true, false, true, 2, 1, 2, RD_BF16, true, false, 0, true>(grid, st, a);
-  if (body == C3_BODY_M16) return c3_go<4, 0, false, false, true, 2, 1, 2, RD_BF16, true, false, 0, true>(grid, st, a);
-  return c3_go<4, 0, false, false, true, 2, 1, 2, RD_BF16, true>(grid, st, a);
+  RD_REQUIRE(wide && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && DT == RD_BF16 && (!headfuse || body == C3_BODY_M16), RD_ESHAPE, "conv16_dev: plain bf16 cout-128 form only");
+  if (body == C3_BODY_M16 && headfuse) return c3_go<4, 0, true, false, true, C3_8x32, RD_BF16, false, 0, true>(grid, st, a);
+  if (body == C3_BODY_M16) return c3_go<4, 0, false, false, true, C3_8x32, RD_BF16, false, 0, true>(grid, st, a);
+  return c3_go<4, 0, false, false, true, C3_8x32, RD_BF16>(grid, st, a);
 #else
   constexpr bool kAllForms = kF16AllForms || DT == RD_BF16;
-  RD_REQUIRE(kAllForms || (fold && w30 && (cout == 128 || hb3 || sw_.conv_wide)) || (headfuse && fold), RD_ESHAPE,
-             "conv3: this fp16 launch form is not instantiated in the emulator build (conv3_has_form)");
+  RD_REQUIRE(kAllForms || fold, RD_ESHAPE, "conv3: this fp16 launch form is not instantiated in the emulator build (conv3_has_form)");
   if (sc) {
     RD_REQUIRE(ts == 0 || ts == 1, RD_ESHAPE, "conv3 + shortcut: tap set %d", ts);
     RD_REQUIRE(fold, RD_EINVAL, "conv3 + shortcut: the weights must carry the folded scales (RD_SCALE_FOLDED)");
   }
-  // (tile shape, cout) -> instantiation; within it (tap set, shortcut).  All of these carry folded scales.
-#define C3_BODY(N, FPW_, FC_, NHB_) C3_BODY_(N, FPW_, FC_, NHB_, false)
-#define C3_BODY_(N, FPW_, FC_, NHB_, WD_)                                                                 \
-  {                                                                                                       \
-    if (sc) return ts == 0 ? c3_go<N, 0, false, true, true, FPW_, FC_, NHB_, DT, WD_>(grid, st, a)        \
-                           : c3_go<N, 1, false, true, true, FPW_, FC_, NHB_, DT, WD_>(grid, st, a);       \
-    return ts == 0 ? c3_go<N, 0, false, false, true, FPW_, FC_, NHB_, DT, WD_>(grid, st, a)               \
-         : ts == 1 ? c3_go<N, 1, false, false, true, FPW_, FC_, NHB_, DT, WD_>(grid, st, a)               \
-                   : c3_go<N, 2, false, false, true, FPW_, FC_, NHB_, DT, WD_>(grid, st, a);              \
-  }
-  if constexpr (kAllForms) { if (th4 && !w30) { if (cout == 128) C3_BODY(4, 2, 2, 2) else C3_BODY(2, 2, 2, 2) } }
   if (body == C3_BODY_M16) {   // v_mfma_f32_16x16x32 form (RD_MFMA16: rd_pack_conv3x3_m16_host made the matching weight image)
-    RD_REQUIRE(wd && fold && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && cin % 32 == 0, RD_ESHAPE,
+    RD_REQUIRE(wide && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && cin % 32 == 0, RD_ESHAPE,
                "conv3: the 16 x 16 x 32 form needs the 8 x 32 tile form: cout 128, folded scales, stride 1, cin a multiple of 32 (cin %d)%s", cin,
                headfuse ? " (rd_conv3x3_mfma16_ok)" : "");
-    if (headfuse) return c3_go<4, 0, true, false, true, 2, 1, 2, DT, true, false, 0, true>(grid, st, a);
-    return c3_go<4, 0, false, false, true, 2, 1, 2, DT, true, false, 0, true>(grid, st, a);
+    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT, false, 0, true>(grid, st, a);
+    return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 0, true>(grid, st, a);
   }
   if (body) {   // heterogeneous tile body (c3_body): the packer made the matching weight image
-    RD_REQUIRE(wd && fold && !headfuse && !g1 && !ph && sw == 1 && a.nchunk % c3_body(body).nu == 0, RD_ESHAPE,
+    RD_REQUIRE(wide && !headfuse && !g1 && !ph && sw == 1 && a.nchunk % c3_body(body).nu == 0, RD_ESHAPE,
                "conv3: tile body %d needs the 8 x 32 tile form with folded scales (%d chunks)", body, a.nchunk);
     if (body == 1) {
       RD_REQUIRE(ts == 1 && !s2, RD_ESHAPE, "conv3: body 1 is the stride-2 pair view");
-      if (sc) { if (cout == 128) return c3_go<4, 1, false, true, true, 2, 1, 2, DT, true, false, 1>(grid, st, a); return c3_go<2, 1, false, true, true, 2, 1, 2, DT, true, false, 1>(grid, st, a); }
-      if (cout == 128) return c3_go<4, 1, false, false, true, 2, 1, 2, DT, true, false, 1>(grid, st, a);
-      return c3_go<2, 1, false, false, true, 2, 1, 2, DT, true, false, 1>(grid, st, a);
+      if (sc) { if (cout == 128) return c3_go<4, 1, false, true, true, C3_8x32, DT, false, 1>(grid, st, a); return c3_go<2, 1, false, true, true, C3_8x32, DT, false, 1>(grid, st, a); }
+      if (cout == 128) return c3_go<4, 1, false, false, true, C3_8x32, DT, false, 1>(grid, st, a);
+      return c3_go<2, 1, false, false, true, C3_8x32, DT, false, 1>(grid, st, a);
     }
     RD_REQUIRE(ts == 0 && !sc, RD_ESHAPE, "conv3: tile body %d takes all nine taps, no shortcut", body);
-    if (body == 2) { if (cout == 128) return c3_go<4, 0, false, false, true, 2, 1, 2, DT, true, false, 2>(grid, st, a); return c3_go<2, 0, false, false, true, 2, 1, 2, DT, true, false, 2>(grid, st, a); }
-    if (cout == 128) return c3_go<4, 0, false, false, true, 2, 1, 2, DT, true, false, 3>(grid, st, a);
-    return c3_go<2, 0, false, false, true, 2, 1, 2, DT, true, false, 3>(grid, st, a);
+    if (body == 2) { if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 2>(grid, st, a); return c3_go<2, 0, false, false, true, C3_8x32, DT, false, 2>(grid, st, a); }
+    if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 3>(grid, st, a);
+    return c3_go<2, 0, false, false, true, C3_8x32, DT, false, 3>(grid, st, a);
   }
   if (ph) {
-    RD_REQUIRE(wd && fold && !sc && !head && !g1 && ts == 3 && sw == 1 && ph->nph >= 1 && ph->nph <= 8, RD_ESHAPE,
+    RD_REQUIRE(wide && !sc && !head && !g1 && ts == 3 && sw == 1 && ph->nph >= 1 && ph->nph <= 8, RD_ESHAPE,
                "conv3: all phases per launch need the 8 x 32 tile form (folded scales, no shortcut / output conv)");
-    if (cout == 128) return c3_go<4, 3, false, false, true, 2, 1, 2, DT, true>(grid, st, a);
-    return c3_go<2, 3, false, false, true, 2, 1, 2, DT, true>(grid, st, a);
+    if (cout == 128) return c3_go<4, 3, false, false, true, C3_8x32, DT>(grid, st, a);
+    return c3_go<2, 3, false, false, true, C3_8x32, DT>(grid, st, a);
   }
-  if (wd && g1) {
-    if (headfuse) return c3_go<4, 0, true, false, true, 2, 1, 2, DT, true, true>(grid, st, a);
-    return c3_go<4, 0, false, false, true, 2, 1, 2, DT, true, true>(grid, st, a);
+  if (wide && g1) {
+    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT, true>(grid, st, a);
+    return c3_go<4, 0, false, false, true, C3_8x32, DT, true>(grid, st, a);
   }
-  if (wd) {
-    if (headfuse) return c3_go<4, 0, true, false, true, 2, 1, 2, DT, true>(grid, st, a);
-    if (cout == 128) C3_BODY_(4, 2, 1, 2, true)
-    C3_BODY_(2, 2, 1, 2, true)
+  if (wide) {   // cout -> instantiation; within it (tap set, shortcut)
+    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT>(grid, st, a);
+#define C3_BODY(N)                                                                                        \
+  {                                                                                                       \
+    if (sc) return ts == 0 ? c3_go<N, 0, false, true, true, C3_8x32, DT>(grid, st, a)                     \
+                           : c3_go<N, 1, false, true, true, C3_8x32, DT>(grid, st, a);                    \
+    return ts == 0 ? c3_go<N, 0, false, false, true, C3_8x32, DT>(grid, st, a)                            \
+         : ts == 1 ? c3_go<N, 1, false, false, true, C3_8x32, DT>(grid, st, a)                            \
+                   : c3_go<N, 2, false, false, true, C3_8x32, DT>(grid, st, a);                           \
   }
-  if (w30) {
-    if (headfuse) return c3_go<4, 0, true, false, true, 2, 1, 2, DT>(grid, st, a);
-    if (cout == 128) C3_BODY(4, 2, 1, 2)
-    if (hb3) C3_BODY(2, 2, 1, 3)
-    if constexpr (kAllForms) C3_BODY(2, 2, 1, 2)
-  }
-  if (head && !sc && fold) return c3_go<4, 0, true, false, true, 4, 2, 2, DT>(grid, st, a);
-  if constexpr (kAllForms) {
-  if (head && !sc) return c3_go<4, 0, true, false, false, 4, 2, 2, DT>(grid, st, a);
-  if (fold) { if (cout == 128) C3_BODY(4, 4, 2, 2) else C3_BODY(2, 4, 2, 2) }
+    if (cout == 128) C3_BODY(4)
+    C3_BODY(2)
 #undef C3_BODY
-#undef C3_BODY_
-  // scale / shift applied in the epilogue (stand-alone use of the C ABI; the lowering always folds)
-#define C3_PLAIN(N) return ts == 0 ? c3_go<N, 0, false, false, false, 4, 2, 2, DT>(grid, st, a) : ts == 1 ? c3_go<N, 1, false, false, false, 4, 2, 2, DT>(grid, st, a) : c3_go<N, 2, false, false, false, 4, 2, 2, DT>(grid, st, a);
-  if (cout == 128) { C3_PLAIN(4) }
-  C3_PLAIN(2)
+  }
+  // 8 x 62: the full-width fused output conv in the 32 x 32 x 16 form, and everything with the scale / shift applied in the epilogue
+  // (stand-alone use of the C ABI; the lowering always folds)
+  if (headfuse && fold) return c3_go<4, 0, true, false, true, C3_8x62, DT>(grid, st, a);
+  if constexpr (kAllForms) {
+    if (headfuse) return c3_go<4, 0, true, false, false, C3_8x62, DT>(grid, st, a);
+    RD_REQUIRE(!fold, RD_ESHAPE, "conv3: folded scales without an output conv take the 8 x 32 tile");
+#define C3_PLAIN(N) return ts == 0 ? c3_go<N, 0, false, false, false, C3_8x62, DT>(grid, st, a) : ts == 1 ? c3_go<N, 1, false, false, false, C3_8x62, DT>(grid, st, a) : c3_go<N, 2, false, false, false, C3_8x62, DT>(grid, st, a);
+    if (cout == 128) { C3_PLAIN(4) }
+    C3_PLAIN(2)
 #undef C3_PLAIN
   }
   return rd::fail(RD_ESHAPE, "conv3: launch form not available");

@@ -275,7 +275,8 @@ int rd_pack_conv3x3_m16_host(const float* w, const float* fold_scale, int cout, 
   return RD_OK;
 }
 int rd_conv3x3_mfma16_ok(int cin, int cout, int stride_w, int W, int fused_output_conv) {
-  return conv3_mfma16_ok(cin, cout, stride_w, W, fused_output_conv != 0) ? 1 : 0;
+  (void)W; (void)fused_output_conv;   // (the form exists at every width, with or without a fused output conv)
+  return conv3_mfma16_ok(cin, cout, stride_w) ? 1 : 0;
 }
 size_t rd_conv1x1_sc_packed_bytes(int cin, int cout) { return sc_frag_bytes(cin, cout); }
 int rd_pack_conv1x1_sc_host(const float* w, const float* fold_scale, int cout, int cin, int dtype, void* out) {
@@ -317,7 +318,7 @@ int rd_conv3x3_bn_act_ex(const void* x, int x_cstride, int x_coff, const void* w
   const bool m16 = (fl & RD_MFMA16) != 0;
   fl &= ~RD_MFMA16;
   const bool folded = (fl & RD_SCALE_FOLDED) != 0;
-  RD_REQUIRE(!m16 || (folded && !sc_x && conv3_mfma16_ok(cin, cout, stride_w, Win, false)), RD_ESHAPE,
+  RD_REQUIRE(!m16 || (folded && !sc_x && conv3_mfma16_ok(cin, cout, stride_w)), RD_ESHAPE,
              "conv3x3_ex: RD_MFMA16 takes folded weights of rd_pack_conv3x3_m16_host: stride 1, cout 128, cin a multiple of 32, no fused shortcut (rd_conv3x3_mfma16_ok)");
   const int body = m16 ? C3_BODY_M16 : stride_w == 2 ? conv3_body_s2(cin, x_cstride, folded) : (sc_x ? 0 : conv3_body_small(cin, folded));
   RD_REQUIRE(!(stride_w == 1 && sc_x && conv3_body_small(cin, folded)), RD_ESHAPE, "conv3x3_ex: at most 16 input channels together with a fused shortcut is not a launch form");
@@ -404,9 +405,7 @@ int rd_conv3x3_bn_act_cat(const void* x1, int x1_cstride, int x1_coff, int cin1,
   RD_REQUIRE(y_coff >= 0 && y_coff + cout <= y_cstride, RD_ESHAPE, "conv3x3_cat: y channels exceed stride");
   RD_REQUIRE(x1_cstride % 8 == 0 && x1_coff % 8 == 0 && x1_coff + cin1 <= x1_cstride && x2_cstride % 8 == 0 && x2_coff % 8 == 0 &&
              x2_coff + cin2 <= x2_cstride, RD_ESHAPE, "conv3x3_cat: channel stride/offset");
-  const DevSwitches& sw_ = dev_switches();
-  RD_REQUIRE(!sw_.conv_v1 && sw_.conv_wide && sw_.conv_w30 && (cout == 64 ? sw_.conv_th4 != 3 : (sw_.conv_th4 && sw_.conv_w30 == 2)), RD_ESHAPE,
-             "conv3x3_cat: needs the 8 x 32 tile form of the persistent 3x3 kernel (a dev switch turned it off)");
+  RD_REQUIRE(!dev_switches().conv_v1, RD_ESHAPE, "conv3x3_cat: needs the persistent 3x3 kernel (RD_CONV_V1 is set)");
   allow_conv_lds();
   Conv3Src2 s2;
   s2.x = x2; s2.cs = x2_cstride; s2.co = x2_coff; s2.cin1 = cin1; s2.cin2 = cin2;
@@ -445,7 +444,7 @@ int rd_conv2d_bn_act_head_out(const void* x, int x_cstride, int x_coff, const vo
   RD_REQUIRE(!dev_switches().conv_v1, RD_EINVAL, "conv2d_head_out: needs the persistent 3x3 kernel (RD_CONV_V1 is set)");
   RD_REQUIRE(!conv3_body_small(cin, (flags & RD_SCALE_FOLDED) != 0), RD_ESHAPE, "conv2d_head_out: cin %d (the packed image of a conv with <= 16 input channels is not this launch form's)", cin);
   const bool m16 = (flags & RD_MFMA16) != 0;
-  RD_REQUIRE(!m16 || ((flags & RD_SCALE_FOLDED) && conv3_mfma16_ok(cin, 128, 1, W, true)), RD_ESHAPE,
+  RD_REQUIRE(!m16 || ((flags & RD_SCALE_FOLDED) && conv3_mfma16_ok(cin, 128, 1)), RD_ESHAPE,
              "conv2d_head_out: RD_MFMA16 (weights of rd_pack_conv3x3_m16_host) is not a launch form for cin %d at width %d (rd_conv3x3_mfma16_ok)", cin, W);
   allow_conv_lds();
   Conv3Args h;
@@ -476,12 +475,6 @@ int rd_conv3x3_bn_act_pair(const void* x0, int x0_coff, const void* w0_packed, c
   RD_REQUIRE(y0 && y1, RD_EINVAL, "conv3x3_pair: null output");
   RD_REQUIRE(y0_coff >= 0 && y1_coff >= 0 && y0_coff + 128 <= y_cstride && y1_coff + 128 <= y_cstride, RD_ESHAPE, "conv3x3_pair: y channels exceed stride");
   allow_conv_lds();
-  if (!conv3_pair_eligible(128, flags, W)) {   // (a dev-switch combination without the two-workgroup 8 x 32 tiles: two launches)
-    if (int rc = launch_conv3(x0, x_cstride, x0_coff, w0_packed, nullptr, shift0, nullptr, 0, 0, y0, y_cstride, y0_coff, B, H, W, cin, 128,
-                              flags, 1, (hipStream_t)stream, 0, nullptr, dtype)) return rc;
-    return launch_conv3(x1, x_cstride, x1_coff, w1_packed, nullptr, shift1, nullptr, 0, 0, y1, y_cstride, y1_coff, B, H, W, cin, 128, flags, 1,
-                        (hipStream_t)stream, 0, nullptr, dtype);
-  }
   Conv3Second g;
   memset(&g, 0, sizeof(g));
   g.x = x1; g.x_co = x1_coff; g.w = w1_packed; g.shift = shift1; g.y = y1; g.y_co = y1_coff;
@@ -500,13 +493,6 @@ int rd_conv2d_bn_act_head_out_pair(const void* x0, int x0_coff, const void* w0_p
   Conv3Args h;
   memset(&h, 0, sizeof(h));
   h.hw = (const unsigned char*)head_w0_packed; h.hb = head_bias0; h.ho = out0; h.ho_bs = out0_batch_stride; h.ho_off = n_off; h.hn = nout0;
-  if (!conv3_pair_eligible(128, flags, W, true)) {
-    if (int rc = launch_conv3(x0, x_cstride, x0_coff, w0_packed, nullptr, shift0, nullptr, 0, 0, nullptr, 128, 0, B, H, W, cin, 128, flags, 1,
-                              (hipStream_t)stream, 0, &h, dtype)) return rc;
-    h.hw = (const unsigned char*)head_w1_packed; h.hb = head_bias1; h.ho = out1; h.ho_bs = out1_batch_stride; h.hn = nout1;
-    return launch_conv3(x1, x_cstride, x1_coff, w1_packed, nullptr, shift1, nullptr, 0, 0, nullptr, 128, 0, B, H, W, cin, 128, flags, 1,
-                        (hipStream_t)stream, 0, &h, dtype);
-  }
   Conv3Second g;
   memset(&g, 0, sizeof(g));
   g.x = x1; g.x_co = x1_coff; g.w = w1_packed; g.shift = shift1;

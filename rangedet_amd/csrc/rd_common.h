@@ -44,10 +44,6 @@ inline int check_launch(const char* what) {
 // (DESIGN.md, table of development switches).
 struct DevSwitches {
   bool conv_v1;            // RD_CONV_V1: generic tap kernel instead of the persistent 3x3 / streaming 1x1 kernels
-  int conv_th4;            // RD_CONV_TH4 (0..3, default 1), RD_CONV_W30 (0..2, default 2), RD_CONV_HEAD30 (0..2, default 1): tile shapes
-  int conv_w30, conv_head30;
-  int conv_hb3;            // RD_CONV_HB3 (default 1): cout 64 on 8 x 30 tiles fetches its halo two units ahead (three buffers)
-  int conv_wide;           // RD_CONV_WIDE (default 1): 8 x 32 tiles (34-pixel halo pitch, every MFMA column live) instead of 8 x 30
   int conv_xcd;            // RD_CONV_XCD (default 1): XCD-aware tile order of the persistent 3x3 kernel (k_conv3.h Conv3Args::xcd)
   int conv_body;           // RD_CONV_BODY (default 1): heterogeneous tile bodies (k_conv3.h c3_body) for stride 2 / <= 16-channel chunks
   bool sort_no_select;     // RD_SORT_NO_SELECT
@@ -61,18 +57,13 @@ struct DevSwitches {
 // what a process launches never depends on who started it (VERDICT r5 / ADVICE r4: a packed weight image and the launch that reads it
 // chose their tap order from RD_CONV_BODY independently).  -DRD_DEV_SWITCHES (RD_EXTRA_HIPCC_FLAGS of rangedet_amd.build, the emulator
 // build of the test tier) brings the environment back for A/B runs of one change on one box.
-constexpr DevSwitches kDevSwitchDefaults = {false, 1, 2, 1, 1, 1, 1, 1, false, false, 0, false, 8, false};
+constexpr DevSwitches kDevSwitchDefaults = {false, 1, 1, false, false, 0, false, 8, false};
 #ifdef RD_DEV_SWITCHES
 inline const DevSwitches& dev_switches() {
   static const DevSwitches s = [] {
     auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
     DevSwitches d = kDevSwitchDefaults;
     d.conv_v1 = getenv("RD_CONV_V1") != nullptr;
-    d.conv_th4 = num("RD_CONV_TH4", 1);
-    d.conv_w30 = num("RD_CONV_W30", 2);
-    d.conv_head30 = num("RD_CONV_HEAD30", 1);
-    d.conv_hb3 = num("RD_CONV_HB3", 1);
-    d.conv_wide = num("RD_CONV_WIDE", 1);
     d.conv_body = num("RD_CONV_BODY", 1);
     d.conv_xcd = num("RD_CONV_XCD", 1);
     d.sort_no_select = getenv("RD_SORT_NO_SELECT") != nullptr;

@@ -172,6 +172,14 @@ def test_conv_fused_with_head_out(be, case):
     assert L.raw("rd_conv2d_bn_act_head_out")(buf, 128, 0, buf, buf, buf, 1, 4, 8, 128, 4, buf, buf, buf, 100, 0, 8, F32, be.stream) == R.RD_EINVAL
 
 
+@pytest.mark.parametrize("be", HIP_ONLY, indirect=True)
+def test_conv_fused_with_head_out_tile_switch(be):
+    """The same checks just past the width (1400) at which the folded 32 x 32 x 16 launch goes from the 8 x 32 to the 8 x 62 tile: one shape
+    (partial second row block, one whole 32-channel chunk) through 8 x 62 folded, 8 x 62 un-folded and the 8 x 32 RD_MFMA16 form.
+    (GPU only: 49 s under the emulator, more than any other case of the test; milliseconds on the GPU.)"""
+    test_conv_fused_with_head_out(be, (1, 9, 1410, 32, 8))
+
+
 @pytest.mark.parametrize("be", BOTH, indirect=True)
 @pytest.mark.parametrize("case", [(2, 9, 70, 128, True, BF16), (1, 8, 64, 72, False, BF16), (3, 17, 40, 64, True, BF16), (2, 9, 70, 128, True, F16),
                                   (1, 8, 33, 72, False, F16)])
