@@ -29,6 +29,9 @@
  *   rd_assign3d_v2            processing_cxx.assign3D_v2                          operator_cxx/src_cxx/assigner.h:11-85
  *   rd_get_point_num          processing_cxx.get_point_num                        operator_cxx/src_cxx/assigner.h:87-109
  *   rd_input_transform        test-time input transform chain                     rangedet/core/input.py:14-42,89-229,522-624
+ *   rd_train_transform        training-time input chain: the same plus Bbox3dAssigner, GenerateTarget and the training
+ *                             FPN targets                                         rangedet/core/input.py:276-320,323-519,522-624,
+ *                                                                                 operator_cxx/src_cxx/assigner.h:11-109
  *
  * Conventions
  *   - every function returns an int status (RD_OK == 0, negative = error); nothing aborts or exits.
@@ -423,6 +426,39 @@ int rd_input_transform(const float* range_image, const float* pc_vehicle_frame, 
                        const rd_input_norm_t* norm_host, int B, int H, int W, int Hp, int Wp, float* input_data,
                        float* coord_s1, float* pc_s1, float* pc_s2, float* pc_s4, float* mask_s1, float* mask_s2,
                        float* mask_s4, void* stream);
+
+/* ---- training-time input chain on the device: rd_input_transform + Bbox3dAssigner + GenerateTarget + the training FPN targets ----
+ * rangedet/core/input.py:276-320,323-519,522-624 and operator_cxx/src_cxx/assigner.h:11-109 with the training name lists of
+ * config/rangedet/rangedet_veh_wo_aug_4_18e.py:72-81,295-305,316-326,336 (one class), for a whole batch in two launches: (1) the box
+ * index of every unpadded pixel's post-ProcessMissValue point (the comparisons of rd_assign3d_v2) and the points per box, (2) all
+ * named tensors.  Every pointer of rd_train_outputs_t is a device pointer; the struct itself is read on the host at call time.
+ * Level l has stride s = 2^l and samples columns s/2, s/2 + s, ...:
+ *   input_data (B,8,Hp,Wp), coord_s1 (B,3,Hp,Wp), pc[l] (B,Hp*Wp/s,3): what rd_input_transform writes
+ *   mask[l] (B,1,Hp,Wp/s): the fill-propagated validity mask, NOT multiplied by the range interval (config:78-81)
+ *   reg_target[l], reg_weight[l], reg_normalize_weight[l] (B,8,Hp,Wp/s) and cls_target[l] (B,1,Hp,Wp/s): each multiplied by the level's
+ *     interval mask on the clipped unnormalised range (input.py:582-597).  reg_target of a pixel in a box with (x,y,z,l,w,h,yaw), point p,
+ *     az = atan2f(p.y, p.x), r = Rz(-az) (xyz - p): (sign(r.x) sqrt|r.x|, sign(r.y) sqrt|r.y|, log w, log l, cos(yaw - az),
+ *     sin(yaw - az), z - h/2, log h) in float32 (input.py:469-503); reg_weight = reg_weight_host there; reg_normalize_weight =
+ *     1 / (points in the pixel's box) on all 8 channels (IEEE divide); cls_target = 1.  Zero for pixels without a box and in the padding.
+ *   bbox3d_ind (B,H,W) int32: index of the first containing box, -1 for none (Bbox3dAssigner's bbox3d_ind_of_each_pt)
+ * Inputs: range_image (B,H,W,4), pc_vehicle_frame (B,H,W,3), inclination (B,H), norm_host as for rd_input_transform;
+ * gt_bbox_imu (B,Mmax,24), gt_bbox_center (B,Mmax,3), gt_limits (B,6) = max_x min_x max_y min_y max_z min_z of the frame's boxes,
+ * gt_bbox_csa (B,Mmax,7); frame b uses its first num_gt_host[b] boxes (read at call time).  radius and max_dist are compared with SQUARED
+ * centre distances like in rd_assign3d_v2 (the reference passes 100 and 20, input.py:299,309).  reg_weight_host: 8 floats.
+ * RD_ESHAPE: Wp % 4 != 0, Hp < H, Wp < W, H or W < 3, Mmax < 1, a num_gt outside 1..min(Mmax, 500) (MAX_BOX_NUM, assigner.h:92).
+ * RD_EWORKSPACE: ws_bytes < rd_train_transform_workspace_bytes(B) (the workspace is zeroed on the stream). */
+typedef struct {
+  float *input_data, *coord_s1;
+  float *pc[3], *mask[3];
+  float *reg_target[3], *reg_weight[3], *reg_normalize_weight[3], *cls_target[3];
+  int* bbox3d_ind;
+} rd_train_outputs_t;
+size_t rd_train_transform_workspace_bytes(int B);
+int rd_train_transform(const float* range_image, const float* pc_vehicle_frame, const float* inclination,
+                       const rd_input_norm_t* norm_host, const float* gt_bbox_imu, const float* gt_bbox_center,
+                       const float* gt_limits, const float* gt_bbox_csa, const int* num_gt_host, int Mmax, float radius,
+                       float max_dist, const float* reg_weight_host, int B, int H, int W, int Hp, int Wp,
+                       const rd_train_outputs_t* out_host, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

@@ -7,3 +7,8 @@ from . import rangedet_veh_wo_aug_4_18e as _base
 def get_config(is_train=False, **kw):
     kw.setdefault("variant", 'ped')
     return _base.get_config(is_train, sampling_rate=4, end_epoch=18, name=__name__.rsplit(".")[-1], **kw)
+
+
+def get_train_transform(**kw):
+    kw.setdefault("variant", 'ped')
+    return _base.get_train_transform(**kw)

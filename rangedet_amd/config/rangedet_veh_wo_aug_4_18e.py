@@ -2,13 +2,16 @@
 param-class and attribute names (General, KvstoreParam, BackboneParam, RpnParam, DetParam, TestParam, ModelParam ...
 cited lines: :30-161 model params, :198-215 TestParam).  ``get_config(is_train=False)`` builds the test symbol at call
 time exactly like the reference does at import (:153-161).  Training-only classes (OptimizeParam, AugParam, target
-generation) are out of scope; ``get_config(True)`` raises.
+generation) are out of scope; ``get_config(True)`` raises.  ``get_train_transform`` gives the training-time transform list with
+its data / label names (:346-378) on its own: the input side of training runs on the device (rangedet_amd.core.input), the loss
+graph does not exist here.
 
 The ped / all_36e variants differ only in class + sampling + epochs; ``variant`` covers them.
 """
 from ..core import detection_metric as metric
-from ..core.input import (CombineData, FilterGTClass, GenerateFPNTarget, GetCoordinates, GetUnnormalizedRange, LoadGTInfo,
-                          LoadRecord, NormData, PadData, ProcessMissValue, SepAndClipData, TransAndReshape, TransposeData)
+from ..core.input import (Bbox3dAssigner, CombineData, FilterGTClass, GenerateFPNTarget, GenerateTarget, GetCoordinates,
+                          GetFixedLengthGTBbox, GetUnnormalizedRange, LoadGTInfo, LoadRecord, NormData, PadData, ProcessMissValue,
+                          SepAndClipData, TransAndReshape, TransposeData)
 from ..mxnext.complicate import normalizer_factory
 from ..symbol.backbone.dla_backbone import DLABackbone as Backbone
 from ..symbol.head.builder import RangeRCNN as Detector
@@ -198,3 +201,76 @@ def get_config(is_train=False, variant="veh", feat_size=(64, 2650), pad_field=(6
                   [metric.ScalarLoss("cls-s{}".format(s), ["rpn_cls_loss_s{}_output".format(s)], []) for s in FpnParam.fpn_strides]
     return General, KvstoreParam, RpnParam, RoiParam, BboxParam, DatasetParam, ModelParam, OptimizeParam, TestParam, \
         transform, data_name, label_name, metric_list, LabelMapParam
+
+
+def get_train_transform(variant="veh", feat_size=(64, 2650), pad_field=(64, 2656)):
+    """(transform, data_name, label_name) of the reference's training branch (config:346-378), built from this package's
+    classes with the reference's parameter values; ``core.input.run_chain(transform, records)`` runs it as one fused device call
+    per batch.  One class per config (the ped / veh variants); the mixed 'kitti' variant has no training chain."""
+    V = _VARIANTS[variant]
+    if len(V["label_set"]) != 1:
+        raise NotImplementedError("training chain: one class per config (GenerateTarget, input.py:383-384); variant %r has %d" %
+                                  (variant, len(V["label_set"])))
+    _fs, _pf = tuple(feat_size), tuple(pad_field)
+    strides = (1, 2, 4)
+    targets = ['rpn_cls_target', 'rpn_reg_target', 'rpn_reg_weight', 'reg_normalize_weight']
+
+    class FpnParam:                                       # config:68-81 (training branch)
+        fpn_strides = strides
+        strategy = 'range'
+        interval = {1: (30, 100), 2: (15, 30), 4: (0, 15)}
+        name_list = list(targets)
+        name_list_without_mask = ['pc_vehicle_frame', 'range_image_mask', 'coord']
+
+    class GenerateTargetParam:                            # config:217-221
+        feat_size = _fs
+        reg_weight = [3, 1, 1, 1, 1, 1, 1, 1]
+        label_set = V["label_set"]
+        num_classes = len(label_set)
+
+    class ClipDataParam:                                  # config:245-255
+        clip_data_dict = {'range_value': (0, 80), 'intensity': (0, 1), 'elongation': (0, 1), 'pc_vehicle_frame_x': (-80, 80),
+                          'pc_vehicle_frame_y': (-80, 80), 'pc_vehicle_frame_z': (-5, 10), 'inclination': (-0.5, 0.1),
+                          'azimuth': (-6.283185307179586, 1.5707963267948966)}
+
+    class NormDataParam:                                  # config:257-267 (mean, variance)
+        norm_data_dict = {'range_value': (20.0, 1500.0), 'intensity': (0.1, 0.01), 'elongation': (7.2558375e-02, 2.6764875e-02),
+                          'pc_vehicle_frame_x': (1.5672500e+00, 3.0740625e+02), 'pc_vehicle_frame_y': (9.8824875e-01, 2.1913250e+02),
+                          'pc_vehicle_frame_z': (1.4, 1.0), 'inclination': (-8.8427375e-02, 9.9001750e-03),
+                          'azimuth': (-7.8061250e-03, 2.5494125e+00)}
+
+    class CombineDataParam:                               # config:269-282
+        combine_name_dict = {'input_data': ['range_value', 'intensity', 'elongation', 'pc_vehicle_frame_x', 'pc_vehicle_frame_y',
+                                            'pc_vehicle_frame_z', 'inclination', 'azimuth']}
+
+    class GetFixedLengthGTBboxParam:                      # config:284-286
+        class_type = V["filter_class"]
+        fixed_length = 200
+
+    class Bbox3dAssignerParam:                            # config:288-289
+        feat_size = _fs
+
+    class PadDataParam:                                   # config:291-305 (training branch)
+        pad_short, pad_long = _pf
+        pad_name_list = ['input_data', 'rpn_cls_target', 'rpn_reg_target', 'rpn_reg_weight', 'reg_normalize_weight',
+                         'range_image_mask', 'pc_vehicle_frame', 'unnormalized_range', 'coord']
+
+    class TransposeDataParam:                             # config:316-326 (training branch)
+        transpose_name_dict = {n: (2, 0, 1) for n in ['input_data', 'rpn_cls_target', 'rpn_reg_target', 'rpn_reg_weight',
+                                                      'reg_normalize_weight', 'range_image_mask', 'pc_vehicle_frame',
+                                                      'unnormalized_range', 'coord']}
+
+    class TransAndReshapeParam:                           # config:336 (training branch)
+        name_list = ['pc_vehicle_frame_s1', 'pc_vehicle_frame_s2', 'pc_vehicle_frame_s4']
+
+    transform = [LoadRecord(), LoadGTInfo(), FilterGTClass(V["label_set"]), ProcessMissValue(), SepAndClipData(ClipDataParam),
+                 GetUnnormalizedRange(), NormData(NormDataParam), GetCoordinates(), CombineData(CombineDataParam),
+                 GetFixedLengthGTBbox(GetFixedLengthGTBboxParam), Bbox3dAssigner(Bbox3dAssignerParam),
+                 GenerateTarget(GenerateTargetParam), PadData(PadDataParam), TransposeData(TransposeDataParam),
+                 GenerateFPNTarget(FpnParam), TransAndReshape(TransAndReshapeParam)]            # config:347-366
+    data_name = ["input_data"]                                                                 # config:367
+    label_name = ["rpn_reg_target_s{}".format(s) for s in strides] + ["rpn_reg_weight_s{}".format(s) for s in strides] + \
+        ["range_image_mask_s{}".format(s) for s in strides] + ["reg_normalize_weight_s{}".format(s) for s in strides] + \
+        ["pc_vehicle_frame_s{}".format(s) for s in strides] + ['gt_bbox_{}_for_iou_pred'.format(V["class_names"][0])] + \
+        ['coord_s1']                                                                           # config:369-378
+    return transform, data_name, label_name

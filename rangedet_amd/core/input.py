@@ -5,12 +5,16 @@ TransAndReshape(TransAndReshapeParam)]`` list (config:380-399) builds and runs u
 
 Design (not the reference's): the image-sized stages do not touch pixels on the host.  LoadRecord reads the raw arrays;
 every stage from ProcessMissValue to GenerateFPNTarget only RECORDS its parameters in the record's chain description;
-TransAndReshape -- the last stage of the test chain -- validates that description and launches ONE fused kernel
-(rd_input_transform, csrc/k_input.h) that writes the named float32 tensors the graph consumes (input_data, coord_s1,
-pc_vehicle_frame_s{1,2,4}, range_image_mask_s{1,2,4}) on the device.  ``run_chain(transform, records)`` does the same for a
-whole batch of records with one launch.  The per-object stages (LoadGTInfo, FilterGTClass, GetFixedLengthGTBbox) are small
-host-side array edits and run as such; Bbox3dAssigner runs on the GPU (rd_assign3d_v2); GenerateTarget (training targets)
-is outside the inference path and raises.
+TransAndReshape -- the last stage of both chains -- validates that description and launches the fused entry point:
+  * the test-time chain (config:380-399, TEST_CHAIN): rd_input_transform (csrc/k_input.h) writes input_data, coord_s1,
+    pc_vehicle_frame_s{1,2,4}, range_image_mask_s{1,2,4};
+  * the training chain (config:346-366, TRAIN_CHAIN): rd_train_transform (csrc/k_target.h) writes those (the masks without the
+    range interval, config:78-81) plus bbox3d_ind, rpn_reg_target / rpn_reg_weight / reg_normalize_weight / rpn_cls_target _s{1,2,4},
+    i.e. Bbox3dAssigner, GenerateTarget and the training FPN targets for the whole batch in two launches.
+``run_chain(transform, records)`` does either for a whole batch of records.  The per-object stages (LoadGTInfo, FilterGTClass,
+GetFixedLengthGTBbox) are small host-side array edits and run as such.  Bbox3dAssigner.apply, called directly, runs on the GPU
+(rd_assign3d_v2) per record; inside run_chain's training chain it and GenerateTarget are recorded like the image stages.
+GenerateTarget.apply on a record without a recorded chain, or for more than one class, raises.
 
 Semantics of every stage: rangedet/core/input.py (cited per class); checked against the numpy restatement in
 oracle/input_ref.py by tests/test_kernels.py::test_input_transform and tests/test_core_input.py.
@@ -173,6 +177,10 @@ class Bbox3dAssigner(DetectionAugmentation):
     def __init__(self, param=None):
         self.height, self.width = param.feat_size[0], param.feat_size[1]
 
+    def record(self, input_record):
+        """Inside run_chain's training chain: the fused entry point computes the assignment for the whole batch."""
+        _stage(input_record, "Bbox3dAssigner", feat_size=(self.height, self.width))
+
     @staticmethod
     def _state_after_earlier_stages(input_record):
         ri = np.asarray(input_record['range_image'], np.float32)
@@ -193,6 +201,8 @@ class Bbox3dAssigner(DetectionAugmentation):
 
     def apply(self, input_record):
         from .. import processing_cxx
+        if _CHAIN in input_record:
+            self.record(input_record)
         gt = np.asarray(input_record['gt_bbox_imu'], np.float32)
         pc, mask = self._state_after_earlier_stages(input_record)
         lim = [float(f(gt[:, :, a])) for a in range(3) for f in (np.max, np.min)]
@@ -203,14 +213,23 @@ class Bbox3dAssigner(DetectionAugmentation):
 
 
 class GenerateTarget(DetectionAugmentation):
-    """rangedet/core/input.py:323-519 builds the TRAINING regression / classification targets; training is outside the
-    inference path this package implements, so the stage can be constructed but not applied."""
+    """rangedet/core/input.py:323-519, the TRAINING regression / classification targets: recorded like the image stages and
+    computed on the device by rd_train_transform (csrc/k_target.h).  The stage needs a recorded chain to join (LoadRecord starts
+    one) and supports one class: the reference's own one-hot reshape (:383-384) fails for more."""
 
     def __init__(self, param):
         self.param = param
 
     def apply(self, input_record):
-        raise NotImplementedError("GenerateTarget produces training targets; rangedet_amd implements the inference path")
+        if _CHAIN not in input_record:
+            raise NotImplementedError("GenerateTarget runs as part of a recorded chain (LoadRecord ... TransAndReshape); this record "
+                                      "carries none")
+        p = self.param
+        if p.num_classes != 1:
+            raise NotImplementedError("GenerateTarget: num_classes %r; the device chain (like the reference's reshape, "
+                                      "input.py:383-384) handles one class" % (p.num_classes,))
+        _stage(input_record, "GenerateTarget", reg_weight=tuple(p.reg_weight), label_set=tuple(p.label_set),
+               num_classes=p.num_classes, feat_size=tuple(p.feat_size))
 
 
 class PadData(DetectionAugmentation):
@@ -261,21 +280,39 @@ class TransAndReshape(DetectionAugmentation):
 # ---- the fused execution of a recorded chain -----------------------------------------------------------------------------------
 TEST_CHAIN = ["LoadRecord", "ProcessMissValue", "SepAndClipData", "GetUnnormalizedRange", "NormData", "GetCoordinates",
               "CombineData", "PadData", "TransposeData", "GenerateFPNTarget", "TransAndReshape"]
+# config:347-365, every stage by name (the host-side ones do not record themselves)
+TRAIN_CHAIN = ["LoadRecord", "LoadGTInfo", "FilterGTClass", "ProcessMissValue", "SepAndClipData", "GetUnnormalizedRange", "NormData",
+               "GetCoordinates", "CombineData", "GetFixedLengthGTBbox", "Bbox3dAssigner", "GenerateTarget", "PadData",
+               "TransposeData", "GenerateFPNTarget", "TransAndReshape"]
+_HOST_STAGES = ("LoadGTInfo", "FilterGTClass", "GetFixedLengthGTBbox")
+_TRAIN_RECORDED = [n for n in TRAIN_CHAIN if n not in _HOST_STAGES]
 _COMBINE = ['range_value', 'intensity', 'elongation', 'pc_vehicle_frame_x', 'pc_vehicle_frame_y', 'pc_vehicle_frame_z',
             'inclination', 'azimuth']
+_TARGETS = ['rpn_cls_target', 'rpn_reg_target', 'rpn_reg_weight', 'reg_normalize_weight']      # config:73-77
 
 
-def _describe(rec):
-    """Validate a record's chain against what the fused kernel computes and reduce it to (clip, norm, interval, pad_hw)."""
-    chain = rec.get(_CHAIN)
-    if not chain or [n for n, _ in chain] != TEST_CHAIN:
-        raise NotImplementedError("the device transform runs the reference's test-time chain %s; recorded: %s" %
-                                  (TEST_CHAIN, [n for n, _ in (chain or [])]))
-    p = dict(chain)
+def _describe_common(p):
     if tuple(p["ProcessMissValue"]["range_fill"]) != (80, 0, 0, -1) or tuple(p["ProcessMissValue"]["pc_fill"]) != (0, 0, 0):
         raise NotImplementedError("ProcessMissValue fill values other than [80,0,0,-1] / [0,0,0]")
     if p["CombineData"]["combine"] != {'input_data': _COMBINE}:
         raise NotImplementedError("CombineData: the kernel writes the 8 channels %s as input_data" % _COMBINE)
+
+
+def _describe(rec):
+    """Validate a record's chain against what the fused kernels compute and reduce it to ("test", clip, norm, interval, pad_hw)
+    or ("train", clip, norm, interval, pad_hw, reg_weight)."""
+    chain = rec.get(_CHAIN)
+    names = [n for n, _ in (chain or [])]
+    if names == _TRAIN_RECORDED:
+        return _describe_train(dict(chain))
+    if not chain or names != TEST_CHAIN:
+        if "GenerateTarget" in names:
+            raise NotImplementedError("the device training chain is %s (recorded stages %s); recorded: %s" %
+                                      (TRAIN_CHAIN, _TRAIN_RECORDED, names))
+        raise NotImplementedError("the device transform runs the reference's test-time chain %s; recorded: %s" %
+                                  (TEST_CHAIN, names))
+    p = dict(chain)
+    _describe_common(p)
     fp = p["GenerateFPNTarget"]
     if fp["strides"] != (1, 2, 4) or fp["masked"] != ['range_image_mask'] or sorted(fp["plain"]) != ['coord', 'pc_vehicle_frame']:
         raise NotImplementedError("GenerateFPNTarget: strides (1,2,4), mask on range_image_mask, plain pc_vehicle_frame / coord")
@@ -286,34 +323,67 @@ def _describe(rec):
     want = ['pc_vehicle_frame_s%d' % s for s in (1, 2, 4)] + ['range_image_mask_s%d' % s for s in (1, 2, 4)]
     if sorted(p["TransAndReshape"]["names"]) != sorted(want):
         raise NotImplementedError("TransAndReshape names %s" % p["TransAndReshape"]["names"])
-    return p["SepAndClipData"]["clip"], p["NormData"]["norm"], fp["interval"], tuple(p["PadData"]["pad_hw"])
+    return "test", p["SepAndClipData"]["clip"], p["NormData"]["norm"], fp["interval"], tuple(p["PadData"]["pad_hw"])
+
+
+def _describe_train(p):
+    """The training name lists of config:72-81 (FPN), :295-305 (pad), :316-326 (transpose), :336 (reshape)."""
+    _describe_common(p)
+    fp = p["GenerateFPNTarget"]
+    if fp["strides"] != (1, 2, 4) or sorted(fp["masked"]) != sorted(_TARGETS) or \
+            sorted(fp["plain"]) != ['coord', 'pc_vehicle_frame', 'range_image_mask']:
+        raise NotImplementedError("GenerateFPNTarget (training): strides (1,2,4), mask on %s, plain pc_vehicle_frame / "
+                                  "range_image_mask / coord" % _TARGETS)
+    need = {'input_data', 'range_image_mask', 'pc_vehicle_frame', 'unnormalized_range', 'coord'} | set(_TARGETS)
+    if set(p["PadData"]["names"]) != need or any(tuple(a) != (2, 0, 1) for a in p["TransposeData"]["axes"].values()) or \
+            set(p["TransposeData"]["axes"]) != need:
+        raise NotImplementedError("PadData / TransposeData (training) must cover %s with axes (2,0,1)" % sorted(need))
+    if sorted(p["TransAndReshape"]["names"]) != ['pc_vehicle_frame_s%d' % s for s in (1, 2, 4)]:
+        raise NotImplementedError("TransAndReshape (training) names %s" % p["TransAndReshape"]["names"])
+    gt = p["GenerateTarget"]
+    if len(gt["reg_weight"]) != 8 or gt["num_classes"] != 1 or tuple(gt["feat_size"]) != tuple(p["Bbox3dAssigner"]["feat_size"]):
+        raise NotImplementedError("GenerateTarget: 8 regression weights, one class, the assigner's feat_size; got %s" % (gt,))
+    return ("train", p["SepAndClipData"]["clip"], p["NormData"]["norm"], fp["interval"], tuple(p["PadData"]["pad_hw"]),
+            tuple(float(v) for v in gt["reg_weight"]))
 
 
 _TRANSFORMS = {}
 
 
 def execute_chain(records, lib=None, alloc=None):
-    """ONE rd_input_transform launch for a list of records whose chains were recorded by the stage classes above.
-    Returns the dict of named (B, ...) float32 device tensors (rangedet_amd.input_transform.DeviceInputTransform)."""
-    from ..input_transform import DeviceInputTransform
+    """The fused launch for a list of records whose chains were recorded by the stage classes above: rd_input_transform for the
+    test-time chain, rd_train_transform for the training chain.  Returns the dict of named (B, ...) device tensors
+    (rangedet_amd.input_transform.DeviceInputTransform / DeviceTrainTransform)."""
+    from ..input_transform import DeviceInputTransform, DeviceTrainTransform
     desc = [_describe(r) for r in records]
     if any(d != desc[0] for d in desc[1:]):
         raise ValueError("records of one batch must share one chain description")
-    clip, norm, interval, pad_hw = desc[0]
-    key = (repr(sorted(clip.items())), repr(sorted(norm.items())), repr(sorted(interval.items())), pad_hw, id(lib), id(alloc))
+    kind, clip, norm, interval, pad_hw = desc[0][:5]
+    key = (kind, repr(sorted(clip.items())), repr(sorted(norm.items())), repr(sorted(interval.items())), pad_hw, desc[0][5:],
+           id(lib), id(alloc))
     if key not in _TRANSFORMS:
-        _TRANSFORMS[key] = DeviceInputTransform(pad_hw=pad_hw, lib=lib, alloc=alloc, clip=clip, norm=norm, interval=interval)
+        if kind == "train":
+            names = tuple(sorted(k for k in records[0] if k.startswith('gt_bbox_') and k.endswith('_for_iou_pred')))
+            _TRANSFORMS[key] = DeviceTrainTransform(pad_hw=pad_hw, lib=lib, alloc=alloc, clip=clip, norm=norm, interval=interval,
+                                                    reg_weight=desc[0][5], iou_pred_names=names)
+        else:
+            _TRANSFORMS[key] = DeviceInputTransform(pad_hw=pad_hw, lib=lib, alloc=alloc, clip=clip, norm=norm, interval=interval)
     return _TRANSFORMS[key](records)
 
 
 def run_chain(transform, records, lib=None, alloc=None):
-    """Apply a transform list (the config's `transform`) to a batch of records: host-side stages per record, the image
-    stages as one device launch for the whole batch.  Returns (records, named device tensors with batch dim)."""
+    """Apply a transform list (the config's `transform`, test-time or training) to a batch of records: host-side stages per
+    record, the image stages -- in the training chain the assigner and the target generation as well -- as one fused device
+    call for the whole batch.  Returns (records, named device tensors with batch dim)."""
     last = transform[-1] if transform else None
     if not isinstance(last, TransAndReshape):
-        raise NotImplementedError("run_chain expects the test-time chain ending in TransAndReshape")
+        raise NotImplementedError("run_chain expects a chain ending in TransAndReshape")
+    fused = any(isinstance(t, GenerateTarget) for t in transform)       # training: no per-record assigner launch
     for rec in records:
         for t in transform[:-1]:
-            t.apply(rec)
+            if fused and isinstance(t, Bbox3dAssigner):
+                t.record(rec)
+            else:
+                t.apply(rec)
         _stage(rec, "TransAndReshape", names=list(last.name_list))
     return records, execute_chain(records, lib, alloc)

@@ -25,39 +25,35 @@ struct AssignArgs {
 };
 
 // LDS per box: A.x A.y A.z  B.x B.y  C.x C.y  D.x D.y  E.z  cx cy cz  radius
-__global__ __launch_bounds__(256) void assign3d_kernel(AssignArgs a) {
+constexpr int ASSIGN_BOX_F = 14;
+__device__ __forceinline__ void assign_stage_box(float* d, const float* b, const float* center, float radius) {
+  d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
+  d[3] = b[3]; d[4] = b[4];
+  d[5] = b[6]; d[6] = b[7];
+  d[7] = b[9]; d[8] = b[10];
+  d[9] = b[14];
+  d[10] = center[0]; d[11] = center[1]; d[12] = center[2];
+  d[13] = radius;
+}
+struct AssignLimits { float max_x, min_x, max_y, min_y, max_z, min_z, max_dist; };
+// Index of the first of the M staged boxes (bx, LDS) that contains the point, or -1; `live` is the caller's mask / no-label-zone
+// test (:42).  Shared with the training chain (k_target.h).
+__device__ __forceinline__ int assign_find_box(const float* bx, int M, float px, float py, float pz, bool live, const AssignLimits& l) {
   RD_NOCONTRACT_A
-  HIP_DYNAMIC_SHARED(float, bx);
-  for (int j = threadIdx.x; j < a.M; j += 256) {
-    const float* b = a.bbox + (size_t)j * 24;
-    float* d = bx + j * 14;
-    d[0] = b[0]; d[1] = b[1]; d[2] = b[2];
-    d[3] = b[3]; d[4] = b[4];
-    d[5] = b[6]; d[6] = b[7];
-    d[7] = b[9]; d[8] = b[10];
-    d[9] = b[14];
-    d[10] = a.center[j * 3]; d[11] = a.center[j * 3 + 1]; d[12] = a.center[j * 3 + 2];
-    d[13] = a.radius[j];
-  }
-  __syncthreads();
-  const long i = blockIdx.x * 256L + threadIdx.x;
-  if (i >= a.N) return;
   int res = -1;
-  const float px = a.pc[i * 3], py = a.pc[i * 3 + 1], pz = a.pc[i * 3 + 2];
-  bool live = !(a.mask[i] < 0.5f || a.nlz[i] > 0.f);                                   // :42
-  live = live && !(px < a.min_x || px > a.max_x) && !(py < a.min_y || py > a.max_y) && !(pz < a.min_z || pz > a.max_z);
+  live = live && !(px < l.min_x || px > l.max_x) && !(py < l.min_y || py > l.max_y) && !(pz < l.min_z || pz > l.max_z);
   if (live) {
     // squared distance to every centre, summed the way Eigen's unrolled 3-element reduction does: x^2 + (y^2 + z^2)  (:47)
     float best = 0.f;
-    for (int j = 0; j < a.M; ++j) {
-      const float* d = bx + j * 14;
+    for (int j = 0; j < M; ++j) {
+      const float* d = bx + j * ASSIGN_BOX_F;
       const float dx = d[10] - px, dy = d[11] - py, dz = d[12] - pz;
       const float q = dx * dx + (dy * dy + dz * dz);
       best = j == 0 ? q : fminf(best, q);
     }
-    if (!(best > a.max_dist)) {                                                           // :49 (squared distance vs max_dist)
-      for (int j = 0; j < a.M; ++j) {
-        const float* d = bx + j * 14;
+    if (!(best > l.max_dist)) {                                                           // :49 (squared distance vs max_dist)
+      for (int j = 0; j < M; ++j) {
+        const float* d = bx + j * ASSIGN_BOX_F;
         const float dx = d[10] - px, dy = d[11] - py, dz = d[12] - pz;
         if (dx * dx + (dy * dy + dz * dz) > d[13]) continue;                            // :51
         if (pz <= d[2] || pz >= d[9]) continue;                                          // :52
@@ -77,7 +73,18 @@ __global__ __launch_bounds__(256) void assign3d_kernel(AssignArgs a) {
       }
     }
   }
-  a.out[i] = res;
+  return res;
+}
+
+__global__ __launch_bounds__(256) void assign3d_kernel(AssignArgs a) {
+  HIP_DYNAMIC_SHARED(float, bx);
+  for (int j = threadIdx.x; j < a.M; j += 256)
+    assign_stage_box(bx + j * ASSIGN_BOX_F, a.bbox + (size_t)j * 24, a.center + j * 3, a.radius[j]);
+  __syncthreads();
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= a.N) return;
+  const AssignLimits l = {a.max_x, a.min_x, a.max_y, a.min_y, a.max_z, a.min_z, a.max_dist};
+  a.out[i] = assign_find_box(bx, a.M, a.pc[i * 3], a.pc[i * 3 + 1], a.pc[i * 3 + 2], !(a.mask[i] < 0.5f || a.nlz[i] > 0.f), l);   // :42
 }
 
 // counts[k] = number of points with index k (float index, truncated like the reference's implicit conversion)

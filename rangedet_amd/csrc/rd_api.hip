@@ -4,6 +4,7 @@
 #include "k_block.h"
 #include "k_assign.h"
 #include "k_input.h"
+#include "k_target.h"
 #include "k_nms3d.h"
 #include "k_meta.h"
 #include "k_misc.h"
@@ -1012,7 +1013,7 @@ int rd_assign3d_v2(const float* pc, const float* bbox, const float* bbox_center,
   a.pc = pc; a.bbox = bbox; a.center = bbox_center; a.radius = bbox_radius; a.mask = mask; a.nlz = is_in_nlz; a.out = out;
   a.N = N; a.M = M;
   a.max_x = max_x; a.min_x = min_x; a.max_y = max_y; a.min_y = min_y; a.max_z = max_z; a.min_z = min_z; a.max_dist = max_dist;
-  hipLaunchKernelGGL(assign3d_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)M * 14 * 4, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(assign3d_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)M * ASSIGN_BOX_F * 4, (hipStream_t)stream, a);
   return check_launch("assign3d_v2");
 }
 size_t rd_get_point_num_workspace_bytes(void) { return POINT_NUM_MAX_BOXES * sizeof(int); }
@@ -1049,6 +1050,54 @@ int rd_input_transform(const float* range_image, const float* pc_vehicle_frame, 
   ProfScope ps(RD_PROF_LAYOUT, st);
   hipLaunchKernelGGL(input_transform_kernel, dim3((unsigned)(((long)Hp * Wp + 255) / 256), B), dim3(256), 0, st, a);
   return check_launch("input_transform");
+}
+
+// ---- training-time input chain (k_target.h) --------------------------------------------------------------------------
+size_t rd_train_transform_workspace_bytes(int B) { return B > 0 ? (size_t)B * POINT_NUM_MAX_BOXES * sizeof(int) : 0; }
+int rd_train_transform(const float* range_image, const float* pc_vehicle_frame, const float* inclination,
+                       const rd_input_norm_t* norm_host, const float* gt_bbox_imu, const float* gt_bbox_center,
+                       const float* gt_limits, const float* gt_bbox_csa, const int* num_gt_host, int Mmax, float radius,
+                       float max_dist, const float* reg_weight_host, int B, int H, int W, int Hp, int Wp,
+                       const rd_train_outputs_t* out_host, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(range_image && pc_vehicle_frame && inclination && norm_host && gt_bbox_imu && gt_bbox_center && gt_limits && gt_bbox_csa &&
+                 num_gt_host && reg_weight_host && out_host && ws, RD_EINVAL, "train_transform: null pointer");
+  const rd_train_outputs_t& o = *out_host;
+  bool all = o.input_data && o.coord_s1 && o.bbox3d_ind;
+  for (int l = 0; l < 3; ++l)
+    all = all && o.pc[l] && o.mask[l] && o.reg_target[l] && o.reg_weight[l] && o.reg_normalize_weight[l] && o.cls_target[l];
+  RD_REQUIRE(all, RD_EINVAL, "train_transform: null output pointer");
+  RD_REQUIRE(B > 0 && H > 2 && W > 2 && Hp >= H && Wp >= W && Wp % 4 == 0, RD_ESHAPE,
+             "train_transform: shape (%d,%d,%d) -> (%d,%d)", B, H, W, Hp, Wp);
+  RD_REQUIRE(Mmax >= 1, RD_ESHAPE, "train_transform: Mmax %d", Mmax);
+  for (int b = 0; b < B; ++b)
+    RD_REQUIRE(num_gt_host[b] >= 1 && num_gt_host[b] <= std::min(Mmax, POINT_NUM_MAX_BOXES), RD_ESHAPE,
+               "train_transform: num_gt[%d] = %d (1..%d)", b, num_gt_host[b], std::min(Mmax, POINT_NUM_MAX_BOXES));
+  RD_REQUIRE(ws_bytes >= rd_train_transform_workspace_bytes(B), RD_EWORKSPACE, "train_transform: workspace %zu < %zu bytes", ws_bytes,
+             rd_train_transform_workspace_bytes(B));
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(ws, 0, rd_train_transform_workspace_bytes(B), st) != hipSuccess) return fail(RD_EHIP, "train_transform: memset failed");
+  TrainArgs a;
+  a.ri = range_image; a.pc = pc_vehicle_frame; a.incl = inclination;
+  a.gt_imu = gt_bbox_imu; a.gt_center = gt_bbox_center; a.gt_limits = gt_limits; a.gt_csa = gt_bbox_csa;
+  a.ind = o.bbox3d_ind; a.counts = (int*)ws; a.o = o;
+  a.Mmax = Mmax; a.radius = radius; a.max_dist = max_dist;
+  for (int c = 0; c < 8; ++c) a.reg_weight[c] = reg_weight_host[c];
+  a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp;
+  a.n = *norm_host;
+  ProfScope ps(RD_PROF_LAYOUT, st);
+  // the counts of a frame are complete when pass 1 of its chunk has finished: same stream, so pass 2 of the chunk may follow directly
+  for (int b0 = 0; b0 < B; b0 += TRAIN_FRAMES_PER_LAUNCH) {
+    const int nb = std::min(TRAIN_FRAMES_PER_LAUNCH, B - b0);
+    int mmax = 0;
+    for (int i = 0; i < TRAIN_FRAMES_PER_LAUNCH; ++i) {
+      a.num_gt[i] = i < nb ? num_gt_host[b0 + i] : 0;
+      mmax = std::max(mmax, a.num_gt[i]);
+    }
+    a.b0 = b0;
+    hipLaunchKernelGGL(train_assign_kernel, dim3((unsigned)(((long)H * W + 255) / 256), nb), dim3(256), (size_t)mmax * ASSIGN_BOX_F * 4, st, a);
+    hipLaunchKernelGGL(train_write_kernel, dim3((unsigned)(((long)Hp * Wp + 255) / 256), nb), dim3(256), 0, st, a);
+  }
+  return check_launch("train_transform");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------
