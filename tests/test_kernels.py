@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from conftest import BOTH, HIP_ONLY, WITH_LATE_DMA
 from emu_util import bf16_round, empty_nhwc, from_nhwc, h16_round, to_nhwc, bf16_bits_to_f32
+import conv_model as CM
 import meta_model as MM
 from oracle import cpu_ops as O
 from oracle import graph_ref as G
@@ -35,6 +36,23 @@ def _tol(dt, ref):
     # f32: accumulation-order noise only.  16-bit: inputs are pre-rounded to the type so the only error is the output rounding
     # (half an ulp: 2^-9 relative for bf16, 2^-12 for fp16) plus fp32 accumulation.
     return 2e-5 * max(1.0, float(np.abs(ref).max())) if dt == F32 else _ulp(dt) * max(1.0, float(np.abs(ref).max())) + (2e-5 if dt == F16 else 0)
+
+
+def _pe(got, ref64, dt, shift, what=""):
+    """The per-element assertion of the 16-bit conv family (conv_model.py): no element further from the float64 reference on the packer's
+    own weights than half an ulp of ITS binade + fp32 summation noise + the bf16 shift pair.  Prints the worst ratio (pytest -rP)."""
+    CM.assert_fp16_range(ref64, dt)
+    nover, worst = CM.conv_check(got, ref64, dt, shift)
+    print("conv-pe %s %s: %d over, worst err / tol %.3f" % (os.environ.get("PYTEST_CURRENT_TEST", "").rsplit(" ", 1)[0].split("::")[-1], what, nover, worst))
+    assert nover == 0, ("per-element", what, nover, worst)
+
+
+def _pe_head(got, act64, hw, hb, dt, what=""):
+    """... of the fp32 outputs of a fused tower output conv: from the float64 tower activation, rounded to the type (CM.head_check)"""
+    ref, act = CM.head_ref64(act64, hw, hb, dt)
+    nover, worst = CM.head_check(got, ref, act, hw, dt)
+    print("conv-pe %s %s: %d over, worst err / tol %.3f" % (os.environ.get("PYTEST_CURRENT_TEST", "").rsplit(" ", 1)[0].split("::")[-1], what, nover, worst))
+    assert nover == 0, ("per-element", what, nover, worst)
 
 
 def run_conv(be, dt, B, H, W, cin, cout, k, stride, flags, cs_in=None, seed=0):
@@ -65,6 +83,8 @@ def run_conv(be, dt, B, H, W, cin, cout, k, stride, flags, cs_in=None, seed=0):
     raw = be.down(y, np.uint16 if dt in H16 else np.float32, (B, H, Wout, cout))
     got = from_nhwc(raw, dt, cout)
     assert np.abs(got - ref).max() <= _tol(dt, ref), (np.abs(got - ref).max(), _tol(dt, ref))
+    if dt in H16:
+        _pe(got, CM.conv_ref64(x, w, dt, scale=sc, shift=sh, stride=stride, flags=flags, res=res), dt, sh)
 
 
 CONV_CASES = [
@@ -143,6 +163,8 @@ def test_conv_fused_with_head_out(be, case):
     want = np.einsum('oc,bchw->bhwo', hw, act).reshape(B, H * W, nout) + hb
     if unfolded:
         assert np.abs(b[:, off:off + H * W] - want).max() < 2 * _ulp(BF16) * max(1.0, np.abs(want).max())
+        _pe_head(b[:, off:off + H * W], CM.conv_ref64(x, w, BF16, scale=sc, shift=sh, flags=R.RD_RELU_POST), hw, hb, BF16, "un-folded")
+    act64f = CM.conv_ref64(x, w, BF16, scale=sc, shift=sh, fold=True, flags=R.RD_RELU_POST)      # (the folded forms: h16_round(w * s))
     # the production form: scale folded into the 3x3 weights (RD_SCALE_FOLDED), shift through the accumulators
     o3 = be.empty(B * N * nout * 4)
     wpf = be.up(L.pack_conv3x3_ex(w, 1, cs, fold_scale=sc, dtype=BF16))
@@ -150,6 +172,7 @@ def test_conv_fused_with_head_out(be, case):
            R.RD_RELU_POST | R.RD_SCALE_FOLDED, be.ptr(dhp), be.ptr(dhb), be.ptr(o3), N * nout, off, nout, BF16, be.stream)
     c = be.down(o3, np.float32, (B, N, nout))
     assert np.abs(c[:, off:off + H * W] - want).max() < 3 * _ulp(BF16) * max(1.0, np.abs(want).max())
+    _pe_head(c[:, off:off + H * W], act64f, hw, hb, BF16, "folded")
     assert (c[:, :off] == 0).all() and (c[:, off + H * W:] == 0).all()
     if cin % 32 == 0:
         # ... and its 16 x 16 x 32 MFMA form (RD_MFMA16): every product is exact in fp32 and each accumulator adds the same 32-channel
@@ -162,6 +185,7 @@ def test_conv_fused_with_head_out(be, case):
                R.RD_RELU_POST | R.RD_SCALE_FOLDED | R.RD_MFMA16, be.ptr(dhp16), be.ptr(dhb), be.ptr(o4), N * nout, off, nout, BF16, be.stream)
         d = be.down(o4, np.float32, (B, N, nout))
         assert np.abs(d[:, off:off + H * W] - want).max() < 3 * _ulp(BF16) * max(1.0, np.abs(want).max())
+        _pe_head(d[:, off:off + H * W], act64f, hw, hb, BF16, "m16")
         assert np.abs(d - c).max() <= 2e-5 * max(1.0, np.abs(c).max()), np.abs(d - c).max()
         assert (d[:, :off] == 0).all() and (d[:, off + H * W:] == 0).all()
     buf = be.ptr(be.empty(1 << 16))
@@ -222,6 +246,7 @@ def test_conv_pair_equals_two_launches(be, case):
     ref = np.maximum(ref, 0)
     got = from_nhwc(be.down(yp[1], np.uint16, (B, H, W, 128)), dt, 128)
     assert np.abs(got - ref).max() <= 3 * _ulp(dt) * max(1.0, float(np.abs(ref).max()))   # (folded scale: w*s is rounded, not w)
+    _pe(got, CM.conv_ref64(xs[1], ws[1], dt, scale=scs[1], shift=shs[1], fold=True, flags=R.RD_RELU_POST), dt, shs[1])
     # the towers' last convs with their 1x1 output convs: logits (1 output) and deltas (8 outputs) of one level
     nouts = (1, 8)
     hws = [(rng.standard_normal((n, 128)) / np.sqrt(128)).astype(np.float32) for n in nouts]
@@ -276,6 +301,8 @@ def test_deconv2d_bn_act(be, case):
     ref = np.maximum(ref * sc[None, :, None, None] + sh[None, :, None, None], 0) + res
     got = from_nhwc(be.down(y, np.uint16 if dt in H16 else np.float32, (B, H, Wout, cout)), dt, cout)
     assert np.abs(got - ref).max() <= _tol(dt, ref)
+    if dt in H16:
+        _pe(got, CM.conv_ref64(x, w, dt, scale=sc, shift=sh, flags=R.RD_RELU_PRE | R.RD_ADD, res=res, deconv=(s, pw)), dt, sh, "un-folded")
     if dt in H16:   # the production form: BatchNorm scale folded into the weights, shift through the accumulators
         y2 = be.empty(B * H * Wout * cout * 4)
         for ph in range(s):
@@ -284,12 +311,28 @@ def test_deconv2d_bn_act(be, case):
                    B, H, W, cin, cout, k[0], k[1], s, pw, ph, R.RD_RELU_PRE | R.RD_ADD | R.RD_SCALE_FOLDED, dt, be.stream)
         got2 = from_nhwc(be.down(y2, np.uint16, (B, H, Wout, cout)), dt, cout)
         assert np.abs(got2 - ref).max() <= 1.5 * _tol(dt, ref)
+        _pe(got2, CM.conv_ref64(x, w, dt, scale=sc, shift=sh, fold=True, flags=R.RD_RELU_PRE | R.RD_ADD, res=res, deconv=(s, pw)), dt, sh, "folded")
 
 
 @pytest.mark.parametrize("be", WITH_LATE_DMA, indirect=True)
 @pytest.mark.parametrize("case", [(BF16, 2, 9, 70, 128, 128, (3, 8), 4, 2), (BF16, 3, 17, 40, 128, 64, (3, 4), 2, 1), (BF16, 1, 20, 45, 64, 64, (3, 4), 2, 1),
                                   (F16, 2, 9, 70, 128, 64, (3, 8), 4, 2), (F16, 1, 11, 33, 64, 64, (3, 4), 2, 1)])
 def test_deconv2d_all_phases_in_one_launch(be, case):
+    run_deconv_all(be, case)
+
+
+def _kind_inputs(kind, dt, x, w, sc, sh, res, seed, out_axis=0):
+    """kind "normal": the test's own inputs; else conv_model's "relu_sparse" / "scaled" inputs of the same shapes (w keeps its fan-in
+    scale: same std, output channel o times 2^((o % 8) - 4) for "scaled")"""
+    if kind == "normal":
+        return x, w, sc, sh, res
+    fan = 1.0 / float(w.std()) ** 2
+    sc2, sh2 = CM.make_affine(kind, len(sc), seed)
+    return (CM.make_input(kind, x.shape, dt, seed), CM.make_weight(kind, w.shape, fan, seed, out_axis), sc2, sh2,
+            None if res is None else CM.make_residual(kind, res.shape, dt, seed))
+
+
+def run_deconv_all(be, case, kind="normal"):
     """rd_deconv2d_bn_act_all (every output phase of a transposed conv in ONE launch: the tile list is (tile, phase), the tap-set
     side and the weight image change per list entry) == the stride_w per-phase launches of rd_deconv2d_bn_act, bit for bit, and
     within one output rounding of torch's conv_transpose2d (mxnext/simple.py:545-580, dla_backbone.py:117-127).  Shapes: several
@@ -302,6 +345,7 @@ def test_deconv2d_all_phases_in_one_launch(be, case):
     sh = rng.standard_normal(cout).astype(np.float32)
     Wout = (W - 1) * s - 2 * pw + k[1]
     res = h16_round(rng.standard_normal((B, cout, H, Wout)).astype(np.float32), dt)
+    x, w, sc, sh, res = _kind_inputs(kind, dt, x, w, sc, sh, res, 21, out_axis=1)
     L = be.lib
     assert L.raw("rd_deconv2d_all_phases_ok")(k[0], k[1], s, pw, cout, dt) == 1
     assert L.raw("rd_deconv2d_all_phases_ok")(3, 3, 2, 1, cout, dt) == 0          # Wout != 2 Win
@@ -320,6 +364,7 @@ def test_deconv2d_all_phases_in_one_launch(be, case):
     ref = F.conv_transpose2d(torch.from_numpy(x), torch.from_numpy(w), stride=(1, s), padding=(1, pw)).numpy()
     ref = np.maximum(ref * sc[None, :, None, None] + sh[None, :, None, None], 0) + res
     assert np.abs(from_nhwc(b, dt, cout) - ref).max() <= 1.5 * _tol(dt, ref)
+    _pe(from_nhwc(b, dt, cout), CM.conv_ref64(x, w, dt, scale=sc, shift=sh, fold=True, flags=R.RD_RELU_PRE | R.RD_ADD, res=res, deconv=(s, pw)), dt, sh, kind)
     buf = be.ptr(be.empty(1 << 16))
     f = L.raw("rd_deconv2d_bn_act_all")
     assert f(buf, 128, 0, buf, 1 << 20, buf, buf, 64, 0, buf, 64, 0, 1, 4, 8, 128, 64, 3, 8, 4, 2, R.RD_RELU_PRE | R.RD_ADD, dt, be.stream) == R.RD_EINVAL   # not folded
@@ -330,6 +375,10 @@ def test_deconv2d_all_phases_in_one_launch(be, case):
 @pytest.mark.parametrize("be", BOTH, indirect=True)
 @pytest.mark.parametrize("case", [(BF16, 2, 9, 70, 128, True), (BF16, 3, 17, 40, 64, True), (F16, 1, 11, 33, 128, True), (BF16, 1, 8, 64, 128, False)])
 def test_deconv2d_phase_pairs_equal_all_phases(be, case):
+    run_deconv_pairs(be, case)
+
+
+def run_deconv_pairs(be, case, kind="normal"):
     """rd_deconv2d_bn_act_pairs (output phases 2p | 2p+1 of the k(3,8) stride-4 transposed conv as ONE 128-channel problem on the
     cout-128 form of the persistent kernel, dla_backbone.py:117-127 'agg1') == rd_deconv2d_bn_act_all bit for bit: the K order of
     every output element is the same.  With and without the residual; error codes for layers / tensors without the form."""
@@ -342,6 +391,7 @@ def test_deconv2d_phase_pairs_equal_all_phases(be, case):
     sh = rng.standard_normal(cout).astype(np.float32)
     Wout = s * W
     res = h16_round(rng.standard_normal((B, cout, H, Wout)).astype(np.float32), dt)
+    x, w, sc, sh, res = _kind_inputs(kind, dt, x, w, sc, sh, res, 33, out_axis=1)
     L = be.lib
     ok = L.raw("rd_deconv2d_phase_pairs_ok")
     assert ok(3, 8, 4, 2, 64, dt) == 1
@@ -363,6 +413,8 @@ def test_deconv2d_phase_pairs_equal_all_phases(be, case):
     ref = F.conv_transpose2d(torch.from_numpy(x), torch.from_numpy(w), stride=(1, s), padding=(1, pw)).numpy() * sc[None, :, None, None] + sh[None, :, None, None]
     ref = (np.maximum(ref, 0) + res) if with_res else np.maximum(ref, 0)
     assert np.abs(from_nhwc(b, dt, cout) - ref).max() <= 1.5 * _tol(dt, ref)
+    _pe(from_nhwc(b, dt, cout), CM.conv_ref64(x, w, dt, scale=sc, shift=sh, fold=True, flags=(R.RD_RELU_PRE | R.RD_ADD) if with_res else R.RD_RELU_POST,
+                                                res=res if with_res else None, deconv=(s, pw)), dt, sh, kind)
     buf = be.ptr(be.empty(1 << 16))
     f = L.raw("rd_deconv2d_bn_act_pairs")
     assert f(buf, 128, 0, buf, 1 << 20, buf, buf, 64, 0, buf, 64, 0, 1, 4, 8, 128, 64, 3, 4, 2, 1, fl, dt, be.stream) == R.RD_ESHAPE      # stride 2
@@ -760,6 +812,7 @@ def run_conv_ex(be, B, H, W, cin, cout, stride, sc_cin=None, residual=False, sc_
     sc2 = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     sh2 = rng.standard_normal(cout).astype(np.float32)
     Wo = (W - 1) // stride + 1
+    pe = dict(scale=sc2, shift=sh2, fold=fold or m16 or bool(sc_cin), stride=stride, flags=R.RD_RELU_POST)   # conv_ref64's view of the launch
     L = be.lib
     cs = -(-cin // 16) * 16
     ref = F.conv2d(torch.from_numpy(x), torch.from_numpy(w), stride=(1, stride), padding=1).numpy()
@@ -780,6 +833,7 @@ def run_conv_ex(be, B, H, W, cin, cout, stride, sc_cin=None, residual=False, sc_
         args_sc = (be.ptr(be.up(to_nhwc(x0, dt, cstride=s_cs))), s_cs, 0, sc_cin, be.ptr(be.up(L.pack_conv1x1_sc(wsc, fold_scale=scs, dtype=dt))))
         scale_ptr, shift_ptr = None, be.ptr(be.up(sh2 + shs))
         flags |= R.RD_ADD
+        pe.update(shift=sh2 + shs, sc_x=x0, sc_w=wsc, sc_scale=scs)
     else:
         ref = ref * sc2[None, :, None, None] + sh2[None, :, None, None]
         wp = be.up(L.pack_conv3x3_m16(w, sc2, dtype=dt) if m16 else L.pack_conv3x3_ex(w, stride, cs, fold_scale=sc2 if fold else None, dtype=dt))
@@ -793,6 +847,7 @@ def run_conv_ex(be, B, H, W, cin, cout, stride, sc_cin=None, residual=False, sc_
             ref = ref + r
             res_ptr = (be.ptr(be.up(to_nhwc(r, dt))), cout, 0)
             flags |= R.RD_ADD
+            pe.update(res=r, flags=R.RD_ADD | R.RD_RELU_POST)
     ref = np.maximum(ref, 0)
     L.call("rd_conv3x3_bn_act_ex", be.ptr(xin), cs, 0, be.ptr(wp), scale_ptr, shift_ptr, *res_ptr, *args_sc, be.ptr(y), cout, 0,
            B, H, W, cin, cout, stride, flags, dt, be.stream)
@@ -801,6 +856,7 @@ def run_conv_ex(be, B, H, W, cin, cout, stride, sc_cin=None, residual=False, sc_
     # on top of the output rounding of _tol: 1.5x
     tol = 1.5 * _tol(dt, ref)
     assert np.abs(got - ref).max() <= tol, (np.abs(got - ref).max(), tol)
+    _pe(got, CM.conv_ref64(x, w, dt, **pe), dt, pe["shift"])
 
 
 CONV_EX_CASES = [
@@ -887,6 +943,7 @@ def test_conv3x3_cat_two_tensor_input(be, case):
     ref = F.conv2d(torch.from_numpy(xc), torch.from_numpy(w), padding=1).numpy() * sc[None, :, None, None] + sh[None, :, None, None]
     ref = np.maximum(ref, 0)
     assert np.abs(from_nhwc(got, dt, cout) - ref).max() <= 1.5 * _tol(dt, ref)
+    _pe(from_nhwc(got, dt, cout), CM.conv_ref64(xc, w, dt, scale=sc, shift=sh, fold=True, flags=R.RD_RELU_POST), dt, sh)
     # against the single-tensor launch on a shared buffer that holds the same channels: the same numbers (with cin1 = 64, cin2 <= 16
     # the two-tensor launch sums the x2 chunk in another order -- five two-tap steps -- so equal to one output rounding, else bit-equal)
     cs = -(-(c1 + cin2) // 16) * 16
@@ -895,6 +952,7 @@ def test_conv3x3_cat_two_tensor_input(be, case):
     L.call("rd_conv3x3_bn_act_ex", be.ptr(be.up(to_nhwc(xc, dt, cstride=cs))), cs, 0, be.ptr(wp1), None, be.ptr(dsh), None, 0, 0, None, 0, 0, 0, None,
            be.ptr(y2), cout, 0, B, H, W, c1 + cin2, cout, 1, fl, dt, be.stream)
     got2 = be.down(y2, np.uint16, (B, H, W, cout))
+    _pe(from_nhwc(got2, dt, cout), CM.conv_ref64(xc, w, dt, scale=sc, shift=sh, fold=True, flags=R.RD_RELU_POST), dt, sh, "single-tensor")
     if c1 == 64 and cin2 <= 16:
         assert np.abs(from_nhwc(got, dt, cout) - from_nhwc(got2, dt, cout)).max() <= 2 * _ulp(dt) * max(1.0, float(np.abs(ref).max()))
     else:
@@ -911,6 +969,10 @@ def test_conv3x3_cat_two_tensor_input(be, case):
                                   (F16, 2, 9, 40, True, 64, 64), (BF16, 2, 16, 72, True, 16, 8), (F16, 1, 11, 33, True, 16, 5), (BF16, 3, 24, 64, True, 16, 16)],
                          ids=lambda c: "-".join(str(v) for v in c))
 def test_block64_equals_the_two_launches(be, case):
+    run_block64(be, case)
+
+
+def run_block64(be, case, kind="normal"):
     """rd_block64_bn_act (csrc/k_block.h): a 64-channel BasicBlock -- conv1 3x3 + BN + ReLU, conv2 3x3 + BN, + identity or 1x1 projection
     shortcut, ReLU (dla_backbone.py:18-56) -- as ONE launch whose intermediate tensor stays in LDS.  BIT-IDENTICAL to the two
     rd_conv3x3_bn_act_ex launches it replaces (same MFMA sequence per accumulator, the intermediate rounded once like the stored
@@ -927,8 +989,14 @@ def test_block64_equals_the_two_launches(be, case):
     wsc = (rng.standard_normal((64, cin)) / np.sqrt(cin)).astype(np.float32)
     s1, s2, ss = (rng.uniform(0.5, 1.5, 64).astype(np.float32) for _ in range(3))
     t1, t2, ts = (rng.standard_normal(64).astype(np.float32) * 0.3 for _ in range(3))
+    if kind != "normal":
+        x = CM.make_input(kind, x.shape, dt, B + H + W)
+        w1, w2, wsc = (CM.make_weight(kind, v.shape, int(np.prod(v.shape[1:])), i, 0) for i, v in enumerate((w1, w2, wsc)))
+        t1, t2, ts = (t * CM.out_scale(kind, 64) for t in (t1, t2, ts))
+        if kind == "scaled" and not proj:        # identity shortcut: x is added to conv2's output, channel by channel -- give it that scale
+            x = h16_round(np.random.default_rng(3).standard_normal(x.shape).astype(np.float32) * CM.out_scale(kind, 64).reshape(1, -1, 1, 1), dt)
     sh2 = (t2.astype(np.float64) + ts).astype(np.float32) if proj else t2
-    dx = be.up(to_nhwc(x, dt, cstride=xcs))
+    dx = be.up(to_nhwc(x, dt, cstride=xcs) if kind == "normal" else CM.nhwc_filled(x, dt, xcs))
     p1, p2 = be.up(L.pack_conv3x3_ex(w1, 1, xcs, fold_scale=s1, dtype=dt)), be.up(L.pack_conv3x3_ex(w2, 1, 64, fold_scale=s2, dtype=dt))
     psc = be.up(L.pack_conv1x1_sc(wsc, fold_scale=ss, dtype=dt)) if proj else None
     d1, d2 = be.up(t1), be.up(sh2)
@@ -957,10 +1025,13 @@ def test_block64_equals_the_two_launches(be, case):
     w1q, w2q = h16_round(w1 * s1[:, None, None, None], dt), h16_round(w2 * s2[:, None, None, None], dt)
     r1 = np.maximum(F.conv2d(torch.from_numpy(x), torch.from_numpy(w1q), padding=1).numpy() + t1[None, :, None, None], 0)
     assert np.abs(tq - r1).max() <= _tol(dt, r1)
+    _pe(tq, CM.conv_ref64(x, w1, dt, scale=s1, shift=t1, fold=True, flags=R.RD_RELU_POST), dt, t1, "conv1 " + kind)
     r2 = F.conv2d(torch.from_numpy(tq), torch.from_numpy(w2q), padding=1).numpy() + sh2[None, :, None, None]
     r2 = r2 + (F.conv2d(torch.from_numpy(x), torch.from_numpy(h16_round(wsc * ss[:, None], dt))[:, :, None, None]).numpy() if proj else x)
     r2 = np.maximum(r2, 0)
     assert np.abs(from_nhwc(got, dt, 64) - r2).max() <= 1.5 * _tol(dt, r2)
+    _pe(from_nhwc(got, dt, 64), CM.conv_ref64(tq, w2, dt, scale=s2, shift=sh2, fold=True, flags=R.RD_ADD | R.RD_RELU_POST, res=None if proj else x,
+                                               sc_x=x if proj else None, sc_w=wsc if proj else None, sc_scale=ss if proj else None), dt, sh2, "conv2 " + kind)
     f = L.raw("rd_block64_bn_act")
     p = be.ptr(be.empty(1 << 16))
     q = be.ptr(be.empty(1 << 16))
@@ -971,6 +1042,149 @@ def test_block64_equals_the_two_launches(be, case):
     assert f(p, 16, 0, 8, q, q, q, None, q, 64, 0, 1, 4, 8, dt, be.stream) == R.RD_EINVAL                 # first block without its projection shortcut
     assert f(p, 8, 0, 8, q, q, q, q, q, 64, 0, 1, 4, 8, dt, be.stream) == R.RD_ESHAPE                     # 8-channel pitch: the shortcut reads 16 channels per pixel
     assert f(p, 24, 16, 8, q, q, q, q, q, 64, 0, 1, 4, 8, dt, be.stream) == R.RD_ESHAPE                   # ... also behind an offset
+
+
+# ---- per-element parity at the edges of the two tiles that ship (8 x 32: folded scales; 8 x 62: un-folded scales) ---------------------
+def run_conv_edge(be, dt, kind, B, H, W, cin, cout, form, stride=1, xcs=None):
+    """One launch on conv_model's "scaled" / "relu_sparse" inputs against conv_ref64, per element.  form:
+      "fold" / "fold_res"      rd_conv3x3_bn_act_ex, RD_SCALE_FOLDED (8 x 32 tile; <= 16 input channels: the five two-tap steps), + residual
+      "m16" / "m16_res"        ... in the RD_MFMA16 form
+      "sc"                     ... with the cin -> cout 1x1 projection shortcut of a second input of cin channels
+      "unfold" / "unfold_res"  rd_conv3x3_bn_act_ex with the scale array (8 x 62 tile)
+      "api" / "api_res"        rd_conv2d_bn_act (un-folded; the only entry that takes stride 2 at an odd width)
+    Padding channels of the xcs-wide input buffer as the contract has them (CM.nhwc_filled)."""
+    L = be.lib
+    seed = B * 1000 + H * 100 + W + cin
+    res_form = form.endswith("_res")
+    fold = form in ("fold", "fold_res", "m16", "m16_res", "sc")
+    m16 = form.startswith("m16")
+    cs = xcs or -(-cin // 16) * 16
+    Wo = (W - 1) // stride + 1
+    x = CM.make_input(kind, (B, cin, H, W), dt, seed)
+    w = CM.make_weight(kind, (cout, cin, 3, 3), cin * 9, seed)
+    sc, sh = CM.make_affine(kind, cout, seed)
+    flags = R.RD_RELU_POST | (R.RD_ADD if res_form or form == "sc" else 0)
+    pe = dict(scale=sc, shift=sh, fold=fold, stride=stride, flags=flags)
+    xin = be.up(CM.nhwc_filled(x, dt, cs))
+    y = be.empty(B * H * Wo * cout * 2)
+    res_ptr, args_sc = (None, 0, 0), (None, 0, 0, 0, None)
+    if res_form:
+        r = CM.make_residual(kind, (B, cout, H, Wo), dt, seed)
+        res_ptr = (be.ptr(be.up(to_nhwc(r, dt))), cout, 0)
+        pe.update(res=r)
+    if form == "sc":
+        x0 = CM.make_input(kind, (B, cin, H, W), dt, seed + 1)
+        wsc = CM.make_weight(kind, (cout, cin), cin, seed + 1)
+        scs, shs = CM.make_affine(kind, cout, seed + 1)
+        sh = sh + shs
+        args_sc = (be.ptr(be.up(CM.nhwc_filled(x0, dt, cs))), cs, 0, cin, be.ptr(be.up(L.pack_conv1x1_sc(wsc, fold_scale=scs, dtype=dt))))
+        pe.update(shift=sh, sc_x=x0, sc_w=wsc, sc_scale=scs)
+    if form.startswith("api"):
+        wp = be.up(L.pack_conv_weight(h16_round(w, dt), dt))
+        L.call("rd_conv2d_bn_act", be.ptr(xin), cs, 0, be.ptr(wp), be.ptr(be.up(sc)), be.ptr(be.up(sh)), *res_ptr, be.ptr(y), cout, 0,
+               B, H, W, cin, cout, 3, 3, stride, flags, dt, be.stream)
+    else:
+        wp = be.up(L.pack_conv3x3_m16(w, sc, dtype=dt) if m16 else L.pack_conv3x3_ex(w, stride, cs, fold_scale=sc if fold else None, dtype=dt))
+        fl = flags | (R.RD_SCALE_FOLDED if fold and form != "sc" else 0) | (R.RD_MFMA16 if m16 else 0)
+        L.call("rd_conv3x3_bn_act_ex", be.ptr(xin), cs, 0, be.ptr(wp), None if fold else be.ptr(be.up(sc)), be.ptr(be.up(sh)), *res_ptr, *args_sc,
+               be.ptr(y), cout, 0, B, H, W, cin, cout, stride, fl, dt, be.stream)
+    got = from_nhwc(be.down(y, np.uint16, (B, H, Wo, cout)), dt, cout)
+    ref = CM.conv_ref64(x, w, dt, **pe)
+    assert float(np.abs(ref).max()) > 0.5
+    _pe(got, ref, dt, sh, "%s %s" % (form, kind))
+
+
+def _edge_params(cases, late=True, dts=(BF16, F16), kinds=("scaled", "relu_sparse")):
+    """(case, type, input kind) x backend.  GPU only: a case above 0.155 G multiply-adds (the emulator takes ~25 s per G and launch), and
+    the fp16 cases with un-folded scales (the emulator build has the fp16 persistent kernel in its folded forms only, k_conv3.h
+    conv3_has_form).  bf16 also runs with late LDS-DMA on the emulator, fp16 on the plain emulator only, as the neighbouring fp16 tests do."""
+    out = []
+    for c in cases:
+        B, H, W, cin, cout = c[:5]
+        big, unfolded = B * H * W * cin * cout * 9 > 0.155e9, c[5].startswith(("unfold", "api"))
+        for dt in dts:
+            for kind in kinds:
+                bes = HIP_ONLY if big or (unfolded and dt == F16) else (WITH_LATE_DMA if (late and dt == BF16) else BOTH)
+                for b in bes:
+                    out.append(pytest.param(b.values[0], c, dt, kind, marks=b.marks,
+                                            id="%s-%s-%s-%s" % (b.id, "-".join(str(v) for v in c), "bf16" if dt == BF16 else "f16", kind)))
+    return out
+
+
+EDGE_SHAPES = [(1, 7, 31), (1, 8, 32), (2, 9, 33), (1, 17, 65)]    # one partial tile | exactly one tile | one pixel / row past it | 3 x 3 tiles
+EDGE_8x32 = [s + f for s in EDGE_SHAPES for f in [(64, 64, "fold"), (128, 128, "fold_res"), (8, 64, "fold", 1, 16), (72, 128, "fold", 1, 80),
+                                                   (32, 128, "m16"), (128, 128, "m16")]]
+# a 64-channel input in an 80-wide buffer: channels 64..79 are beyond the last k-slot, never read, and hold CM.PAD_PATTERN
+EDGE_8x32 += [(2, 9, 33, 64, 64, "fold_res", 1, 80)]
+# stride (1, 2).  The pair view of rd_conv3x3_bn_act_ex needs an even width; at W = 65 the same two layer shapes go through rd_conv2d_bn_act
+# (un-folded, 8 x 62 tile, every second column stored), the shortcut's place taken by a residual: an odd-width shortcut launch does not exist
+EDGE_S2 = [(1, 9, W, 64, 128, "sc", 2) for W in (64, 66)] + [(1, 9, W, 128, 128, "fold_res", 2) for W in (64, 66)]
+EDGE_S2 += [(1, 9, 65, 64, 128, "api_res", 2), (1, 9, 65, 128, 128, "api_res", 2)]
+EDGE_8x62 = [(1, 8, 62, 128, 64, "unfold"), (1, 9, 63, 64, 128, "unfold"), (2, 7, 125, 64, 64, "unfold_res")]
+# 8 images: 8 x 2 column strips = 16 tiles, a multiple of 8 on the emulator's 8 slots and the GPU's -> the XCD tile order | 8 x 2 x 2 = 32
+# tiles on 8 slots: four per workgroup, row-block and strip carries
+EDGE_B8 = [(8, 8, 64, 64, 128, "fold"), (8, 9, 33, 64, 64, "fold_res")]
+
+
+@pytest.mark.parametrize("be,case,dt,kind", _edge_params(EDGE_8x32) + _edge_params(EDGE_S2), indirect=["be"])
+def test_conv3x3_per_element_at_8x32_tile_edges(be, case, dt, kind):
+    run_conv_edge(be, dt, kind, *case)
+
+
+@pytest.mark.parametrize("be,case,dt,kind", _edge_params(EDGE_8x62), indirect=["be"])
+def test_conv3x3_per_element_at_8x62_tile_edges(be, case, dt, kind):
+    run_conv_edge(be, dt, kind, *case)
+
+
+@pytest.mark.parametrize("be,case,dt,kind", _edge_params(EDGE_B8, kinds=("scaled",)), indirect=["be"])
+def test_conv3x3_per_element_eight_images(be, case, dt, kind):
+    run_conv_edge(be, dt, kind, *case)
+
+
+# the fused block: (dt, B, H, W, projection shortcut, x channel stride, cin) -- both shortcut forms at the three tile-edge shapes (cin 64: also
+# the m16 form), the 64 channels once in an 80-wide buffer, and the network's first block (8 and 5 channels in a 16-channel buffer)
+EDGE_BLOCK = [(B, H, W, proj, 64, 64) for (B, H, W) in EDGE_SHAPES[1:] for proj in (False, True)] + [(2, 9, 33, False, 80, 64), (1, 9, 33, True, 16, 8), (1, 9, 33, True, 16, 5)]
+
+
+def _block_params():
+    out = []
+    for c in EDGE_BLOCK:
+        for dt in (BF16, F16):
+            for kind in ("scaled", "relu_sparse"):
+                # (fp16 on the emulator: the one-tile shape and the first block; a block case is four launches of two convs each)
+                for b in (WITH_LATE_DMA if dt == BF16 else BOTH if (c[:3] == (1, 8, 32) or c[5] < 64) else HIP_ONLY):
+                    out.append(pytest.param(b.values[0], (dt,) + c, kind, marks=b.marks,
+                                            id="%s-%s-%s-%s" % (b.id, "-".join(str(v) for v in c), "bf16" if dt == BF16 else "f16", kind)))
+    return out
+
+
+@pytest.mark.parametrize("be,case,kind", _block_params(), indirect=["be"])
+def test_block64_per_element_at_tile_edges(be, case, kind):
+    """run_block64 on the tile-edge shapes: bit-equality with the two launches (and the m16 form) as in test_block64_equals_the_two_launches,
+    and conv1 / conv2 per element on the "scaled" and "relu_sparse" inputs"""
+    run_block64(be, case, kind)
+
+
+def _deconv_params(cases):
+    out = []
+    for c in cases:
+        for kind in ("scaled", "relu_sparse"):
+            for b in (WITH_LATE_DMA if c[0] == BF16 else BOTH):
+                out.append(pytest.param(b.values[0], c, kind, marks=b.marks, id="%s-%s-%s" % (b.id, "-".join(str(v) for v in c), kind)))
+    return out
+
+
+EDGE_DECONV = [(dt, B, H, W) + f for dt in (BF16, F16) for (B, H, W) in ((1, 9, 33), (2, 8, 32)) for f in ((128, 64, (3, 8), 4, 2), (128, 64, (3, 4), 2, 1))]
+
+
+@pytest.mark.parametrize("be,case,kind", _deconv_params(EDGE_DECONV), indirect=["be"])
+def test_deconv2d_all_phases_per_element_at_tile_edges(be, case, kind):
+    run_deconv_all(be, case, kind)
+
+
+@pytest.mark.parametrize("be,case,kind", _deconv_params([(dt, B, H, W, 128, True) for dt in (BF16, F16) for (B, H, W) in ((1, 9, 33), (2, 8, 32))]), indirect=["be"])
+def test_deconv2d_phase_pairs_per_element_at_tile_edges(be, case, kind):
+    run_deconv_pairs(be, case, kind)
 
 
 @pytest.mark.parametrize("be", BOTH, indirect=True)
