@@ -51,12 +51,6 @@ struct Conv3Args {
   const bf16_t* sx; int s_cs, s_co; long s_bs;
   const unsigned char* scw;  // packed [ks][Cout/32][64 lanes][8 bf16] (pack_sc_frag)
   int s_nks;                 // 16-channel k-steps of the shortcut input (<= 8)
-  // GRP variant: TWO problems of the same shape in one launch (the cls and the reg tower conv of a head level,
-  // head/builder.py:221-240).  Images B .. 2B-1 of the tile list are problem 1; every per-problem pointer / size of problem 1 is
-  // problem 0's plus the delta below (elements of the pointer's type; g_w, g_hw in bytes), and the image index restarts at 0.
-  int ngrp;                  // 1 or 2
-  long g_x, g_res, g_y, g_w, g_shift, g_hw, g_hb, g_ho, g_ho_bs;
-  int g_hn;
   // PH variant (TS == 3): ALL phases of a transposed conv in one launch (dla_backbone.py:117-127, mxnext/simple.py:545-580).  The
   // tile list is (spatial tile, phase) with the phase running fastest inside a workgroup's list, so the nph phases of a tile are
   // computed back to back by one workgroup: its halo comes from HBM once (the re-fetches of the other phases hit L2) instead of
@@ -90,7 +84,9 @@ struct Conv3Args {
 // Tried and retired (profiles/EXPERIMENTS.md): a 4 x 62 two-workgroup tile paid 6/4 instead of 10/8 halo rows per
 // output row and lost to the 8-row two-workgroup tile on every layer class.  An 8 x 30 tile (halo pitch 32) threw away two of every
 // 32 MFMA columns -- 6.25 % of the MFMAs of convs that are MFMA / power bound -- and lost to 8 x 32.  A third halo
-// buffer (fetch two units ahead, cout 64 on 8 x 30) needed the LDS that the 34-pixel pitch now takes.
+// buffer (fetch two units ahead, cout 64 on 8 x 30) needed the LDS that the 34-pixel pitch now takes.  Two convs of the same shape in
+// one launch (the cls and the reg tower conv of a head level) lost end to end every time it was measured: -0.4 .. -0.7 % (round 4),
+// -1.4 % (round 5), -1.1 % (round 6).
 enum C3Tile { C3_8x62 = 0, C3_8x32 = 1 };
 template <int NCT, C3Tile TILE = C3_8x62> struct C3Cfg {
   static constexpr bool WIDE = TILE == C3_8x32;          // every MFMA column live, two workgroups per CU
@@ -330,9 +326,6 @@ inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && co
 // it reads the accumulators, adds the residual if any, converts and clamps.
 // DT = RD_BF16 or RD_F16: the element type of activations and weights (same layouts; the MFMA instruction and the conversions
 // of the epilogue differ, rd_common.h H16<DT>).
-// GRP: two problems per launch (Conv3Args::ngrp): the tile list runs over 2B images, the group of an image selects the input,
-// weight image, shift, residual, output (and fused output conv) -- the launch then has twice the tiles per resident workgroup
-// slot (half the tail round) and one prologue / drain instead of two.  Only for the forms the lowering pairs: FOLD, no SC.
 // M16 (round 6): the MFMAs as v_mfma_f32_16x16x32 instead of 32x32x16.  Under the part's power cap the matrix cores sustain more of the
 // SAME arithmetic in that shape (tools/micro/mfma_power.hip, profiles/r06g_mfma_power.txt: operands from LDS at the same bytes per FLOP,
 // post-ReLU activations against N(0, 0.05) weights: 1 539 -> 1 698 TFLOP/s, shader clock 1 753 -> 2 015 MHz; a 16 x 16 tile moves half the
@@ -343,19 +336,18 @@ inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && co
 // register is free after its 4th MFMA of block 1 and is re-read for the next step right there (single buffered); the barrier, the counted
 // waits and the DMA schedule are those of the 32 x 32 form (12 fragment reads per step in both).
 template <int NCT, int DBG = 0, int TS = 0, bool HEAD = false, bool SC = false, bool FOLD = false, C3Tile TILE = C3_8x62,
-          int DT = RD_BF16, bool GRP = false, int BODY = 0, bool M16 = false>
+          int DT = RD_BF16, int BODY = 0, bool M16 = false>
 __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream_kernel(Conv3Args a) {
   using Cfg = C3Cfg<NCT, TILE>;
   constexpr bool WD = Cfg::WIDE;                 // the 8 x 32 tile
   constexpr int FPW = Cfg::FPW, FC = Cfg::FC;    // pixel fragments per wave (4 or 2), per tile row (2 or 1)
-  static_assert(!M16 || (NCT == 4 && WD && FOLD && !SC && !GRP && TS == 0 && BODY == 0 && DBG == 0),
+  static_assert(!M16 || (NCT == 4 && WD && FOLD && !SC && TS == 0 && BODY == 0 && DBG == 0),
                 "16 x 16 x 32 form: cout 128 on the 8 x 32 tiles, folded scales, all nine taps");
-  static_assert(BODY == 0 || (WD && FOLD && !GRP && !HEAD && (TS == 0 || TS == 1)), "heterogeneous tile bodies: 8 x 32 tiles, folded scales");
-  static_assert(!GRP || (WD && FOLD && !SC), "two problems per launch: 8 x 32 tiles (output-conv weights from L2), folded scales, no shortcut");
+  static_assert(BODY == 0 || (WD && FOLD && !HEAD && (TS == 0 || TS == 1)), "heterogeneous tile bodies: 8 x 32 tiles, folded scales");
   static_assert(!WD || FOLD, "8 x 32 tile: no room for the scale / shift array");
   static_assert(!HEAD || (NCT == 4 && TS == 0), "fused output conv: cout 128, all nine taps");
   constexpr bool PH = TS == 3;                   // all phases of a transposed conv: (tile, phase) list, run-time tap-set side
-  static_assert(!PH || (FOLD && !SC && !HEAD && !GRP), "all-phase transposed conv: folded scales, no shortcut / output conv / second problem");
+  static_assert(!PH || (FOLD && !SC && !HEAD), "all-phase transposed conv: folded scales, no shortcut / output conv");
   static_assert(!(HEAD && SC), "a head tower has no shortcut");
   constexpr int R = Cfg::R, IPW = Cfg::IPW, SLAB = Cfg::SLAB, COUT = NCT * 32;
   constexpr int C3_HALO = Cfg::HALO, C3_HPW = Cfg::HPW, C3_TH = Cfg::TH;
@@ -388,16 +380,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
       bzw[j] = hi ? 0u : ((unsigned)th | ((unsigned)tl << 16));
     }
   };
-  if constexpr (FOLD && !GRP && !M16) load_shift(a.shift);
-  // GRP: the fragment of BOTH problems, loaded once (4 more registers; a reload inside the tile loop would be a vector-memory
-  // load whose wait drains the LDS-DMA queue -- measured +8 .. 12 us per launch); the tile's one is selected per tile
-  unsigned bzw1[GRP ? NCT : 1];
-  if constexpr (GRP) {
-    load_shift(a.shift ? a.shift + a.g_shift : nullptr);
-#pragma unroll
-    for (int j = 0; j < NCT; ++j) bzw1[j] = bzw[j];
-    load_shift(a.shift);
-  }
+  if constexpr (FOLD && !M16) load_shift(a.shift);
   // M16: the shift of MFMA row lane & 15 of fragment cb as the dword {hi, lo}, held by lane quad cb & 3 in register cb >> 2: its two
   // halves are k = 8*(cb & 3), +1 of the A operand, and the rank-1 MFMA of fragment cb takes ones in exactly those two k (2 registers
   // instead of 8 across the MFMA phase)
@@ -490,8 +473,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     hh0 = f_rb * C3_TH - 1;
     hlo = hw0 < 0 ? -hw0 : 0;
     hlim = a.W - hw0;
-    const bool fg = GRP && f_b >= a.B;                     // (GRP) problem 1: its own input, image index from 0
-    htile = (const unsigned char*)(a.x + (size_t)(fg ? f_b - a.B : f_b) * a.x_bs + a.x_co + (fg ? a.g_x : 0)) +
+    htile = (const unsigned char*)(a.x + (size_t)f_b * a.x_bs + a.x_co) +
             ((long)hh0 * a.W + hw0) * (long)a.x_cs * 2;
     if constexpr (WD) {
       if (a.x2) htile2 = (const unsigned char*)(a.x2 + (size_t)f_b * a.x2_bs + a.x2_co) + ((long)hh0 * a.W + hw0) * (long)a.x2_cs * 2;
@@ -548,26 +530,13 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
   };
   int fslot = 0, fslab = 0;                               // ring slot / slab-within-tile of the NEXT slab to fetch
   const int nslab_tile = BODY ? (a.nchunk / BNU) * BG : a.nchunk * NS;
-  // GRP: the slab stream runs R steps ahead of the MFMAs, so it has its own tile cursor -- the weight image is the one of the
-  // problem that tile belongs to (past the end of the list the dummy fetches read whichever image the cursor has reached)
-  // (n0 = how many of this workgroup's tiles wg, wg + G, ... belong to problem 0, i.e. lie below tiles_img * B: one division per
-  //  workgroup instead of a third mixed-radix tile cursor advanced in every step)
-  const int t0_ = tiles_img * a.B;
-  const int n0 = GRP ? (wg < t0_ ? (t0_ - wg + G - 1) / G : 0) : 0;
-  int stile = 0;                                          // ordinal (within the workgroup's list) of the tile the slab stream is in
-  const unsigned char* wsrc = a.w + (GRP && n0 == 0 ? a.g_w : 0);
+  const unsigned char* wsrc = a.w;
   auto slab_piece = [&](int j) {
     dma_s(wsrc + (size_t)fslab * SLAB + (wave * IPW + j) * 1024, lane * 16, RING + fslot * SLAB + (wave * IPW + j) * 1024);
   };
   auto slab_advance = [&]() {
     fslot = fslot + 1 == R ? 0 : fslot + 1;
     fslab = fslab + 1 == nslab_tile ? 0 : fslab + 1;
-    if constexpr (GRP) {
-      if (fslab == 0) {
-        ++stile;
-        wsrc = a.w + (stile >= n0 ? a.g_w : 0);
-      }
-    }
     if constexpr (PH) {   // the slab stream's own phase cursor (it runs R steps ahead of the MFMAs)
       if (fslab == 0) {
         s_ph = s_ph + 1 == nph ? 0 : s_ph + 1;
@@ -859,7 +828,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
         memcpy(&ones, ob, 16);
 #pragma unroll
         for (int n = 0; n < NM; ++n) {
-          unsigned ab[4] = {GRP && k >= n0 ? bzw1[GRP ? n % NCT : 0] : bzw[n % NCT], z0, z0, z0};
+          unsigned ab[4] = {bzw[n % NCT], z0, z0, z0};
           s16x8 bz;
           memcpy(&bz, ab, 16);
           acc[n / NCT][n % NCT] = H16<DT>::mfma(bz, ones, f32x16{});
@@ -898,8 +867,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     // Scratch: this wave's 8 KB of the halo buffer that is free until the next unit's tap-0 barrier
     // (row = one pixel = COUT*2 bytes, 16-byte slot index XORed with the pixel number: conflict-free both ways).
     const int ct = c_ct, rb = c_rb;
-    const bool eg = GRP && c_b >= a.B;                               // (GRP) problem 1: image index from 0, pointers + deltas
-    const int b = eg ? c_b - a.B : c_b;
+    const int b = c_b;
     const int e_ph = c_ph;                                           // (PH) phase of the tile just computed
     if constexpr (PH) {
       // next list entry: the following phase of this tile, then the next tile; its tap-set side becomes the current one, and the
@@ -925,15 +893,15 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     static_assert(32 * CW * 2 <= C3_HALO / 4, "transpose scratch");
     constexpr int ROWB = CW * 2, SPR = CW / 8, RPI = 64 / SPR;   // row bytes, 16-B slots per row, rows per store instr
     unsigned char* scr = smem + hflip(abuf) + wave * (C3_HALO / 4);   // (the buffer of the unit just consumed)
-    bf16_t* __restrict__ yrow0 = a.y + (eg ? a.g_y : 0) + (size_t)b * a.y_bs + (size_t)oh0 * a.Wo * a.y_cs + a.y_co + (PH ? e_ph * a.y_pc : 0);
+    bf16_t* __restrict__ yrow0 = a.y + (size_t)b * a.y_bs + (size_t)oh0 * a.Wo * a.y_cs + a.y_co + (PH ? e_ph * a.y_pc : 0);
     // (base of image b, not of the wave's first row: rows past the image bottom must not even form an address beyond the buffer)
-    const bf16_t* __restrict__ rimg0 = a.res + (eg ? a.g_res : 0) + (size_t)b * a.r_bs + a.r_co + (PH ? e_ph * a.r_pc : 0);
-    // fused output conv of the tile's problem
-    const unsigned char* __restrict__ e_hw = a.hw + (eg ? a.g_hw : 0);
-    const float* __restrict__ e_hb = a.hb + (eg ? a.g_hb : 0);
-    float* __restrict__ e_ho = a.ho + (eg ? a.g_ho : 0);
-    const long e_ho_bs = a.ho_bs + (eg ? a.g_ho_bs : 0);
-    const int e_hn = a.hn + (eg ? a.g_hn : 0);
+    const bf16_t* __restrict__ rimg0 = a.res + (size_t)b * a.r_bs + a.r_co + (PH ? e_ph * a.r_pc : 0);
+    // fused output conv
+    const unsigned char* __restrict__ e_hw = a.hw;
+    const float* __restrict__ e_hb = a.hb;
+    float* __restrict__ e_ho = a.ho;
+    const long e_ho_bs = a.ho_bs;
+    const int e_hn = a.hn;
     const int sh = a.sw - 1;   // stride 2: shift by 1, keep even columns
     if constexpr (SC) {
       // projection shortcut: B operand = this wave's pixels of the block input straight from global memory (lane (m, hi)
@@ -1289,9 +1257,9 @@ inline int conv_num_cus() {
 }
 
 // One launch of one instantiation; the first launch of each raises its dynamic-LDS limit (once per process and instantiation).
-template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, C3Tile TILE, int DT, bool GRP = false, int BODY = 0, bool M16 = false>
+template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, C3Tile TILE, int DT, int BODY = 0, bool M16 = false>
 inline int c3_go(int grid, hipStream_t st, const Conv3Args& a) {
-  auto k = conv3x3_stream_kernel<NCT, 0, TS, HEAD, SC, FOLD, TILE, DT, GRP, BODY, M16>;
+  auto k = conv3x3_stream_kernel<NCT, 0, TS, HEAD, SC, FOLD, TILE, DT, BODY, M16>;
   static std::atomic<unsigned long long> seen{0};
   once_per_device(seen, [&] { allow_big_lds(k); });
   constexpr size_t lds = C3Cfg<NCT, TILE>::LDS + (HEAD && TILE == C3_8x62 ? 16384 : 0);   // (8 x 62 tile: the output conv's weights in LDS)
@@ -1316,14 +1284,6 @@ inline bool conv3_eligible(const TapList& tl, int in_stride, int out_stride, int
   return !dev_switches().conv_v1;
 }
 
-// Second problem of a two-problem launch (GRP): same shapes, channel strides and flags as the first, its own tensors.
-struct Conv3Second {
-  const void* x; int x_co;
-  const void* w; const float* shift;
-  const void* res; int r_co;
-  void* y; int y_co;
-  const void* hw; const float* hb; float* ho; long ho_bs; int hn;   // fused output conv (when the first problem has one)
-};
 // All phases of a transposed conv in one launch (PH form, TS = 3): per-phase weight images w + ph * w_pb, tap-set side per phase
 struct Conv3Phases { int nph, ts_mask, y_pc, r_pc; long w_pb; };
 // Second input tensor of a conv over a channel concatenation [x | x2] (Conv3Args::x2): cin of the launch = cin1 + cin2 where cin1
@@ -1342,25 +1302,24 @@ inline bool conv3_mfma16_ok(int cin, int cout, int stride_w) {
 template <int DT>
 inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, const float* scale, const float* shift,
                            const void* res, int r_cs, int r_co, void* y, int y_cs, int y_co, int B, int H, int W, int cin,
-                           int cout, int flags, int sw, hipStream_t st, int ts, const Conv3Args* head, const Conv3Second* g1,
+                           int cout, int flags, int sw, hipStream_t st, int ts, const Conv3Args* head,
                            const Conv3Phases* ph, const Conv3Src2* s2, int body);
 inline int launch_conv3(const void* x, int x_cs, int x_co, const void* w, const float* scale, const float* shift,
                         const void* res, int r_cs, int r_co, void* y, int y_cs, int y_co, int B, int H, int W, int cin,
                         int cout, int flags, int sw, hipStream_t st, int ts, const Conv3Args* head, int dt,
-                        const Conv3Second* g1, const Conv3Phases* ph, const Conv3Src2* s2, int body) {
+                        const Conv3Phases* ph, const Conv3Src2* s2, int body) {
   RD_REQUIRE(is_h16(dt), RD_EINVAL, "conv3: dtype %d (the persistent 3x3 kernel takes RD_BF16 or RD_F16)", dt);
-  if (dt == RD_F16) return launch_conv3_dt<RD_F16>(x, x_cs, x_co, w, scale, shift, res, r_cs, r_co, y, y_cs, y_co, B, H, W, cin, cout, flags, sw, st, ts, head, g1, ph, s2, body);
-  return launch_conv3_dt<RD_BF16>(x, x_cs, x_co, w, scale, shift, res, r_cs, r_co, y, y_cs, y_co, B, H, W, cin, cout, flags, sw, st, ts, head, g1, ph, s2, body);
+  if (dt == RD_F16) return launch_conv3_dt<RD_F16>(x, x_cs, x_co, w, scale, shift, res, r_cs, r_co, y, y_cs, y_co, B, H, W, cin, cout, flags, sw, st, ts, head, ph, s2, body);
+  return launch_conv3_dt<RD_BF16>(x, x_cs, x_co, w, scale, shift, res, r_cs, r_co, y, y_cs, y_co, B, H, W, cin, cout, flags, sw, st, ts, head, ph, s2, body);
 }
 
 template <int DT>
 inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, const float* scale, const float* shift,
                            const void* res, int r_cs, int r_co, void* y, int y_cs, int y_co, int B, int H, int W, int cin,
-                           int cout, int flags, int sw, hipStream_t st, int ts, const Conv3Args* head, const Conv3Second* g1,
+                           int cout, int flags, int sw, hipStream_t st, int ts, const Conv3Args* head,
                            const Conv3Phases* ph, const Conv3Src2* s2, int body) {
   Conv3Args a;
   memset(&a, 0, sizeof(a));
-  a.ngrp = g1 ? 2 : 1;
   a.nph = 1;
   if (ph) { a.nph = ph->nph; a.ts_mask = ph->ts_mask; a.y_pc = ph->y_pc; a.r_pc = ph->r_pc; a.w_pb = ph->w_pb; }
   if (head) { a.hw = head->hw; a.hb = head->hb; a.ho = head->ho; a.ho_bs = head->ho_bs; a.ho_off = head->ho_off; a.hn = head->hn; }
@@ -1384,36 +1343,21 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
   // With a fused output conv on that tile the conv's 16 KB of weights no longer fit in LDS and are re-read from L2 per fragment and
   // pass; measured per layer: W = 1328 213 -> 205 us, W = 664 109 -> 107 us, W = 2656 398 -> 405 us, so the full-width level stays
   // on the 8 x 62 tile -- unless it is in the 16 x 16 x 32 form, where the two-workgroup tile wins at full width too (W 2656:
-  // 352 -> 328 us, +0.5 % frames/s on one box, profiles/EXPERIMENTS.md), or a two-problem launch, whose output-conv weights are per
-  // problem and come from L2.  Un-folded scales (stand-alone use of the C ABI) need the scale / shift array in LDS: 8 x 62.
+  // 352 -> 328 us, +0.5 % frames/s on one box, profiles/EXPERIMENTS.md).  Un-folded scales (stand-alone use of the C ABI) need the
+  // scale / shift array in LDS: 8 x 62.
   const bool headfuse = head && !sc;
   RD_REQUIRE(!headfuse || cout == 128, RD_ESHAPE, "conv3 + output conv: cout %d (128)", cout);
-  const bool wide = fold && (!headfuse || W <= 1400 || body == C3_BODY_M16 || g1);
+  const bool wide = fold && (!headfuse || W <= 1400 || body == C3_BODY_M16);
   const int tw = wide ? C3Cfg<4, C3_8x32>::TW : C3Cfg<4, C3_8x62>::TW, th = C3Cfg<4>::TH;
-  a.ncol = (W + tw - 1) / tw; a.nrow = (H + th - 1) / th; a.ntiles = a.ncol * a.nrow * B * a.ngrp;
-  if (g1) {
-    RD_REQUIRE(wide && fold && !sc && ts == 0 && cout == 128 && sw == 1, RD_ESHAPE,
-               "conv3: two problems per launch need the 8 x 32 tile form (cout 128, folded scales, stride 1, no shortcut)");
-    RD_REQUIRE(!headfuse == !g1->hw && !res == !g1->res && !shift == !g1->shift, RD_EINVAL,
-               "conv3: the two problems of a launch must have the same structure (output conv / residual / shift)");
-    a.g_x = ((const bf16_t*)g1->x + g1->x_co) - ((const bf16_t*)x + x_co);
-    a.g_w = (const unsigned char*)g1->w - (const unsigned char*)w;
-    a.g_shift = shift ? g1->shift - shift : 0;
-    a.g_res = res ? ((const bf16_t*)g1->res + g1->r_co) - ((const bf16_t*)res + r_co) : 0;
-    a.g_y = y ? ((bf16_t*)g1->y + g1->y_co) - ((bf16_t*)y + y_co) : 0;
-    if (headfuse) {
-      a.g_hw = (const unsigned char*)g1->hw - a.hw; a.g_hb = g1->hb - a.hb; a.g_ho = g1->ho - a.ho;
-      a.g_ho_bs = g1->ho_bs - a.ho_bs; a.g_hn = g1->hn - a.hn;
-    }
-  }
+  a.ncol = (W + tw - 1) / tw; a.nrow = (H + th - 1) / th; a.ntiles = a.ncol * a.nrow * B;
   if (s2) {   // conv over [x | x2]: cin = cin1 + cin2, the first cin1 (full 32-channel chunks) from x
-    RD_REQUIRE(wide && !g1 && sw == 1 && s2->cin1 > 0 && s2->cin1 % 32 == 0 && s2->cin1 + s2->cin2 == cin && s2->cin2 > 0, RD_ESHAPE,
+    RD_REQUIRE(wide && sw == 1 && s2->cin1 > 0 && s2->cin1 % 32 == 0 && s2->cin1 + s2->cin2 == cin && s2->cin2 > 0, RD_ESHAPE,
                "conv3: a two-tensor input needs the 8 x 32 tile form and cin1 a multiple of 32 (cin1 %d, cin2 %d, cin %d)", s2->cin1, s2->cin2, cin);
     a.x2 = (const bf16_t*)s2->x; a.x2_cs = s2->cs; a.x2_co = s2->co; a.x2_bs = (long)H * W * s2->cs;
     a.nchunk1 = s2->cin1 / 32; a.nslots2 = cin_slots(s2->cin2, RD_BF16); a.nslots = a.nchunk1 * 4;
   }
   const int grid = std::min(a.ntiles, conv_num_cus() * (wide ? 2 : 1));
-  a.xcd = dev_switches().conv_xcd && !g1 && (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
+  a.xcd = dev_switches().conv_xcd && (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
   if (conv_trace_buf() && (size_t)grid * 8 <= (1u << 20)) a.trace = conv_trace_buf();
   ProfScope ps(RD_PROF_CONV3, st);
 #ifdef RD_CONV3_DEV   // ablation variants (bf16; DBG bits: 2 no barrier, 4 no DMA after the prologue, 16 halo from the zero page, 32 no vmcnt wait)
@@ -1425,7 +1369,7 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
   // plain conv with folded scales on the 8 x 32 tile, cout 32 * N: (also) 8 no MFMAs, 64 residual from one L2-resident pixel, 128 no residual
   // load, 256 halo from the first MB of x (L2-resident REAL data), 1 no stores
 #define C3_DBG(N, D)                                                                                                    \
-  if (cout == 32 * N && wide && !head && !g1 && !ph && !s2 && !body && sw == 1 && ts == 0 && DT == RD_BF16 && dbg == D) { \
+  if (cout == 32 * N && wide && !head && !ph && !s2 && !body && sw == 1 && ts == 0 && DT == RD_BF16 && dbg == D) { \
     auto k = conv3x3_stream_kernel<N, D, 0, false, false, true, C3_8x32>; allow_big_lds(k);                             \
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<N, C3_8x32>::LDS), st, a);                                      \
     return check_launch("conv3x3_stream_kernel<dbg>");                                                                  \
@@ -1435,9 +1379,9 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
 #undef C3_DBG
 #endif
 #ifdef RD_CONV3_DEV_M16_ONLY   // tools/micro/conv16_dev.hip: only the plain cout-128 form on the 8 x 32 tiles, in its two MFMA shapes (a one-minute build)
-  RD_REQUIRE(wide && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && DT == RD_BF16 && (!headfuse || body == C3_BODY_M16), RD_ESHAPE, "conv16_dev: plain bf16 cout-128 form only");
-  if (body == C3_BODY_M16 && headfuse) return c3_go<4, 0, true, false, true, C3_8x32, RD_BF16, false, 0, true>(grid, st, a);
-  if (body == C3_BODY_M16) return c3_go<4, 0, false, false, true, C3_8x32, RD_BF16, false, 0, true>(grid, st, a);
+  RD_REQUIRE(wide && !sc && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && DT == RD_BF16 && (!headfuse || body == C3_BODY_M16), RD_ESHAPE, "conv16_dev: plain bf16 cout-128 form only");
+  if (body == C3_BODY_M16 && headfuse) return c3_go<4, 0, true, false, true, C3_8x32, RD_BF16, 0, true>(grid, st, a);
+  if (body == C3_BODY_M16) return c3_go<4, 0, false, false, true, C3_8x32, RD_BF16, 0, true>(grid, st, a);
   return c3_go<4, 0, false, false, true, C3_8x32, RD_BF16>(grid, st, a);
 #else
   constexpr bool kAllForms = kF16AllForms || DT == RD_BF16;
@@ -1447,35 +1391,31 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
     RD_REQUIRE(fold, RD_EINVAL, "conv3 + shortcut: the weights must carry the folded scales (RD_SCALE_FOLDED)");
   }
   if (body == C3_BODY_M16) {   // v_mfma_f32_16x16x32 form (RD_MFMA16: rd_pack_conv3x3_m16_host made the matching weight image)
-    RD_REQUIRE(wide && !sc && !g1 && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && cin % 32 == 0, RD_ESHAPE,
+    RD_REQUIRE(wide && !sc && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && cin % 32 == 0, RD_ESHAPE,
                "conv3: the 16 x 16 x 32 form needs the 8 x 32 tile form: cout 128, folded scales, stride 1, cin a multiple of 32 (cin %d)%s", cin,
                headfuse ? " (rd_conv3x3_mfma16_ok)" : "");
-    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT, false, 0, true>(grid, st, a);
-    return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 0, true>(grid, st, a);
+    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT, 0, true>(grid, st, a);
+    return c3_go<4, 0, false, false, true, C3_8x32, DT, 0, true>(grid, st, a);
   }
   if (body) {   // heterogeneous tile body (c3_body): the packer made the matching weight image
-    RD_REQUIRE(wide && !headfuse && !g1 && !ph && sw == 1 && a.nchunk % c3_body(body).nu == 0, RD_ESHAPE,
+    RD_REQUIRE(wide && !headfuse && !ph && sw == 1 && a.nchunk % c3_body(body).nu == 0, RD_ESHAPE,
                "conv3: tile body %d needs the 8 x 32 tile form with folded scales (%d chunks)", body, a.nchunk);
     if (body == 1) {
       RD_REQUIRE(ts == 1 && !s2, RD_ESHAPE, "conv3: body 1 is the stride-2 pair view");
-      if (sc) { if (cout == 128) return c3_go<4, 1, false, true, true, C3_8x32, DT, false, 1>(grid, st, a); return c3_go<2, 1, false, true, true, C3_8x32, DT, false, 1>(grid, st, a); }
-      if (cout == 128) return c3_go<4, 1, false, false, true, C3_8x32, DT, false, 1>(grid, st, a);
-      return c3_go<2, 1, false, false, true, C3_8x32, DT, false, 1>(grid, st, a);
+      if (sc) { if (cout == 128) return c3_go<4, 1, false, true, true, C3_8x32, DT, 1>(grid, st, a); return c3_go<2, 1, false, true, true, C3_8x32, DT, 1>(grid, st, a); }
+      if (cout == 128) return c3_go<4, 1, false, false, true, C3_8x32, DT, 1>(grid, st, a);
+      return c3_go<2, 1, false, false, true, C3_8x32, DT, 1>(grid, st, a);
     }
     RD_REQUIRE(ts == 0 && !sc, RD_ESHAPE, "conv3: tile body %d takes all nine taps, no shortcut", body);
-    if (body == 2) { if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 2>(grid, st, a); return c3_go<2, 0, false, false, true, C3_8x32, DT, false, 2>(grid, st, a); }
-    if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, false, 3>(grid, st, a);
-    return c3_go<2, 0, false, false, true, C3_8x32, DT, false, 3>(grid, st, a);
+    if (body == 2) { if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, 2>(grid, st, a); return c3_go<2, 0, false, false, true, C3_8x32, DT, 2>(grid, st, a); }
+    if (cout == 128) return c3_go<4, 0, false, false, true, C3_8x32, DT, 3>(grid, st, a);
+    return c3_go<2, 0, false, false, true, C3_8x32, DT, 3>(grid, st, a);
   }
   if (ph) {
-    RD_REQUIRE(wide && !sc && !head && !g1 && ts == 3 && sw == 1 && ph->nph >= 1 && ph->nph <= 8, RD_ESHAPE,
+    RD_REQUIRE(wide && !sc && !head && ts == 3 && sw == 1 && ph->nph >= 1 && ph->nph <= 8, RD_ESHAPE,
                "conv3: all phases per launch need the 8 x 32 tile form (folded scales, no shortcut / output conv)");
     if (cout == 128) return c3_go<4, 3, false, false, true, C3_8x32, DT>(grid, st, a);
     return c3_go<2, 3, false, false, true, C3_8x32, DT>(grid, st, a);
-  }
-  if (wide && g1) {
-    if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT, true>(grid, st, a);
-    return c3_go<4, 0, false, false, true, C3_8x32, DT, true>(grid, st, a);
   }
   if (wide) {   // cout -> instantiation; within it (tap set, shortcut)
     if (headfuse) return c3_go<4, 0, true, false, true, C3_8x32, DT>(grid, st, a);

@@ -342,12 +342,13 @@ __global__ __launch_bounds__(256) void wnms_prep_kernel(const float* __restrict_
 // around the ego vehicle are different cells), and which ones differs from row to row: walking the columns in lock step left
 // three of four lanes idle during every polygon clip.  Each lane now first collects the columns IT has to clip (a 32-bit mask:
 // later position, not suppressed in round 1, common cell), then all lanes clip their own next candidate together; a lane idles
-// only once its list is shorter than the longest of its wave.  Tile width (RD_WNMS_CT): 8 columns = 2 +- 1.2 candidates per lane,
-// longest of a wave ~ 5, against 8 lock-step column steps before: batched NMS of 8 frames 793 -> 726 us, +0.8 % frames/s; wider
-// tiles balance better (32 columns: 8 +- 2.4, longest ~ 14) but leave the GPU with a quarter of the waves and longer serial
-// chains per wave: 16 columns 820 us, 32 columns 1 103 us -- the kernel is bound by the latency of a wave's chain of clips, not
-// by lane utilisation.
-template <int WN_CT, bool BAL>        // columns per tile: 8 (default), 16 or 32 (RD_WNMS_CT, A/B); BAL: the wave's candidates dealt out evenly
+// only once its list is shorter than the longest of its wave.  Tile width: 8 columns = 2 +- 1.2 candidates per lane,
+// longest of a wave ~ 5, against 8 lock-step column steps before: batched NMS of 8 frames 793 -> 726 us, +0.8 % frames/s.
+// Tried and retired (profiles/EXPERIMENTS.md round 3): wider tiles balance better (32 columns: 8 +- 2.4, longest ~ 14) but leave the
+// GPU with a quarter of the waves and longer serial chains per wave: 16 columns 820 us, 32 columns 1 103 us.  The wave's candidates
+// compacted through LDS and dealt out evenly over the lanes (rows from an LDS copy, result bits by LDS atomics, two more barriers
+// per tile): 726 -> 790 us.  The kernel is bound by the latency of a wave's chain of clips, not by lane utilisation, so the lists
+// stay lane-private and lock-free.
 __global__ __launch_bounds__(64) void wnms_pairs_kernel(const float* __restrict__ prep, int cap,
                                                         const int* __restrict__ d_count, float thresh, float thresh_vote,
                                                         int is3d, unsigned long long* __restrict__ thr,
@@ -369,12 +370,10 @@ __global__ __launch_bounds__(64) void wnms_pairs_kernel(const float* __restrict_
     supp_state += blockIdx.z * (bs.ints / 2);
   }
   if (nrb <= 0) return;
+  constexpr int WN_CT = 8;            // columns per tile
   constexpr int WN_SUB = 64 / WN_CT;  // tiles per 64-column mask word
   __shared__ float colp[WN_CT * PREP_F];
   __shared__ float edges[EDGE_LDS_BYTES / 4];
-  __shared__ float rowp[BAL ? PREP_F * 64 : 1];              // BAL: the tile's 64 prepped rows, [field][row]
-  __shared__ unsigned short plist[BAL ? 64 * WN_CT : 1];     // BAL: candidate pairs (row << 5 | column)
-  __shared__ unsigned mbits[BAL ? 128 : 1];                  // BAL: thr / vote bits per row
   const int t = threadIdx.x;
   EdgeLds EL;
   EL.ax = edges; EL.ay = edges + 512; EL.bx = edges + 1024; EL.by = edges + 1536; EL.an = edges + 2048;
@@ -424,51 +423,16 @@ __global__ __launch_bounds__(64) void wnms_pairs_kernel(const float* __restrict_
         if (!w_share_cell(mc, oc) || (allow_skip && w_pair_skippable(mine, &colp[c * PREP_F]))) cand &= ~(1u << c);
       }
     }
-    if constexpr (BAL) {
-      // the wave's candidates, compacted and dealt out one per lane and turn: lane t clips pairs t, t + 64, ... of the list,
-      // so every lane takes ceil(n / 64) turns whatever its own row's share was.  Rows come from an LDS copy (k-major: the
-      // write is conflict-free), result bits are ORed into per-row LDS words.
-      if (cand) {
-#pragma unroll
-        for (int k = 0; k < PREP_F; ++k) rowp[k * 64 + t] = mine[k];
-      }
-      const int cnt = __popc(cand);
-      int incl = cnt;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (t >= d) incl += v;
-      }
-      const int total = __shfl(incl, 63);
-      int pos = incl - cnt;
-      for (unsigned rem = cand; rem; rem &= rem - 1u) plist[pos++] = (unsigned short)((t << 5) | (__ffs(rem) - 1));
-      mbits[t] = 0u;
-      mbits[64 + t] = 0u;
-      __syncthreads();
-      for (int i = t; i < total; i += 64) {
-        const int pr = plist[i], r = pr >> 5, c = pr & 31;
-        float a[PREP_F];
-#pragma unroll
-        for (int k = 0; k < PREP_F; ++k) a[k] = rowp[k * 64 + r];
-        const float ovr = w_overlap(a, &colp[c * PREP_F], is3d != 0, EL);
-        if (ovr >= thresh) atomicOr(&mbits[r], 1u << c);
-        if (ovr > thresh_vote) atomicOr(&mbits[64 + r], 1u << c);
-      }
-      __syncthreads();
-      mt = mbits[t];
-      mv = mbits[64 + t];
-      if (!active) continue;
-    } else {
-      if (!active) continue;
-      while (cand) {
-        const int c = __ffs(cand) - 1;
-        cand &= cand - 1u;
-        float ovr = w_overlap(mine, &colp[c * PREP_F], is3d != 0, EL);
-        if (ovr >= thresh) mt |= 1u << c;
-        if (ovr > thresh_vote) mv |= 1u << c;
-      }
+    if (!active) continue;
+    while (cand) {
+      const int c = __ffs(cand) - 1;
+      cand &= cand - 1u;
+      float ovr = w_overlap(mine, &colp[c * PREP_F], is3d != 0, EL);
+      if (ovr >= thresh) mt |= 1u << c;
+      if (ovr > thresh_vote) mv |= 1u << c;
     }
-    typedef typename std::conditional<WN_CT == 32, unsigned, typename std::conditional<WN_CT == 16, unsigned short, unsigned char>::type>::type part_t;
+    typedef unsigned char part_t;                          // one WN_CT-bit part of a mask word
+    static_assert(WN_CT == 8, "part_t holds the WN_CT bits of a tile");
     ((part_t*)thr)[((size_t)q1 * nwcap + cb) * WN_SUB + sub] = (part_t)mt;   // (little endian: part `sub` holds bits WN_CT*sub ..)
     ((part_t*)vote)[((size_t)q1 * nwcap + cb) * WN_SUB + sub] = (part_t)mv;
   }

@@ -325,7 +325,7 @@ int rd_conv3x3_bn_act_ex(const void* x, int x_cstride, int x_coff, const void* w
   RD_REQUIRE(!(stride_w == 1 && sc_x && conv3_body_small(cin, folded)), RD_ESHAPE, "conv3x3_ex: at most 16 input channels together with a fused shortcut is not a launch form");
   return launch_conv3(x, x_cstride * v, x_coff, w_packed, scale, shift, residual, r_cstride, r_coff, y, y_cstride, y_coff, B, H,
                       Wv, ex_view_cin(cin, x_cstride, stride_w), cout, fl, 1, (hipStream_t)stream, stride_w == 2 ? 1 : 0,
-                      sc_x ? &e : nullptr, dtype, nullptr, nullptr, nullptr, body);
+                      sc_x ? &e : nullptr, dtype, nullptr, nullptr, body);
 }
 
 // ---- a whole 64-channel BasicBlock in one launch (k_block.h) ------------------------------------------------------------------------
@@ -411,7 +411,7 @@ int rd_conv3x3_bn_act_cat(const void* x1, int x1_cstride, int x1_coff, int cin1,
   Conv3Src2 s2;
   s2.x = x2; s2.cs = x2_cstride; s2.co = x2_coff; s2.cin1 = cin1; s2.cin2 = cin2;
   return launch_conv3(x1, x1_cstride, x1_coff, w_packed, nullptr, shift, nullptr, 0, 0, y, y_cstride, y_coff, B, H, W, cin1 + cin2, cout, flags,
-                      1, (hipStream_t)stream, 0, nullptr, dtype, nullptr, nullptr, &s2, conv3_body_cat(cin1, cin2, true));
+                      1, (hipStream_t)stream, 0, nullptr, dtype, nullptr, &s2, conv3_body_cat(cin1, cin2, true));
 }
 
 // ---- last tower conv + the tower's 1x1 output conv in one launch (bf16) ---------------------------------------------
@@ -452,54 +452,7 @@ int rd_conv2d_bn_act_head_out(const void* x, int x_cstride, int x_coff, const vo
   memset(&h, 0, sizeof(h));
   h.hw = (const unsigned char*)head_w_packed; h.hb = head_bias; h.ho = out; h.ho_bs = out_batch_stride; h.ho_off = n_off; h.hn = nout;
   return launch_conv3(x, x_cstride, x_coff, w_packed, scale, shift, nullptr, 0, 0, nullptr, 128, 0, B, H, W, cin, 128, flags & ~RD_MFMA16, 1,
-                      (hipStream_t)stream, 0, &h, dtype, nullptr, nullptr, nullptr, m16 ? C3_BODY_M16 : 0);
-}
-
-// ---- the cls and the reg tower conv of a head level as ONE launch (two problems of the same shape) -------------------------
-static int pair_checks(const char* fn, const void* x0, const void* x1, const void* w0, const void* w1, const float* shift0,
-                       const float* shift1, int x_cstride, int x0_coff, int x1_coff, int B, int H, int W, int cin, int flags,
-                       int dtype) {
-  RD_REQUIRE(x0 && x1 && w0 && w1 && shift0 && shift1, RD_EINVAL, "%s: null pointer", fn);
-  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "%s: dtype %d (RD_BF16 or RD_F16)", fn, dtype);
-  RD_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0, RD_ESHAPE, "%s: shape", fn);
-  RD_REQUIRE((flags & RD_SCALE_FOLDED) && !(flags & RD_ADD), RD_EINVAL, "%s: needs RD_SCALE_FOLDED weights, takes no residual", fn);
-  RD_REQUIRE(x_cstride % 8 == 0 && x0_coff % 8 == 0 && x1_coff % 8 == 0 && x0_coff + cin_slots(cin, RD_BF16) * 8 <= x_cstride &&
-             x1_coff + cin_slots(cin, RD_BF16) * 8 <= x_cstride, RD_ESHAPE, "%s: x channel stride/offset", fn);
-  RD_REQUIRE(!dev_switches().conv_v1, RD_EINVAL, "%s: needs the persistent 3x3 kernel (RD_CONV_V1 is set)", fn);
-  RD_REQUIRE(cin > 16, RD_ESHAPE, "%s: cin %d (more than 16 input channels)", fn, cin);
-  return RD_OK;
-}
-int rd_conv3x3_bn_act_pair(const void* x0, int x0_coff, const void* w0_packed, const float* shift0, void* y0, int y0_coff,
-                           const void* x1, int x1_coff, const void* w1_packed, const float* shift1, void* y1, int y1_coff,
-                           int x_cstride, int y_cstride, int B, int H, int W, int cin, int flags, int dtype, void* stream) {
-  if (int rc = pair_checks("conv3x3_pair", x0, x1, w0_packed, w1_packed, shift0, shift1, x_cstride, x0_coff, x1_coff, B, H, W, cin, flags, dtype)) return rc;
-  RD_REQUIRE(y0 && y1, RD_EINVAL, "conv3x3_pair: null output");
-  RD_REQUIRE(y0_coff >= 0 && y1_coff >= 0 && y0_coff + 128 <= y_cstride && y1_coff + 128 <= y_cstride, RD_ESHAPE, "conv3x3_pair: y channels exceed stride");
-  allow_conv_lds();
-  Conv3Second g;
-  memset(&g, 0, sizeof(g));
-  g.x = x1; g.x_co = x1_coff; g.w = w1_packed; g.shift = shift1; g.y = y1; g.y_co = y1_coff;
-  return launch_conv3(x0, x_cstride, x0_coff, w0_packed, nullptr, shift0, nullptr, 0, 0, y0, y_cstride, y0_coff, B, H, W, cin, 128, flags, 1,
-                      (hipStream_t)stream, 0, nullptr, dtype, &g);
-}
-int rd_conv2d_bn_act_head_out_pair(const void* x0, int x0_coff, const void* w0_packed, const float* shift0, const void* head_w0_packed,
-                                   const float* head_bias0, float* out0, long out0_batch_stride, int nout0,
-                                   const void* x1, int x1_coff, const void* w1_packed, const float* shift1, const void* head_w1_packed,
-                                   const float* head_bias1, float* out1, long out1_batch_stride, int nout1,
-                                   int x_cstride, long n_off, int B, int H, int W, int cin, int flags, int dtype, void* stream) {
-  if (int rc = pair_checks("conv2d_head_out_pair", x0, x1, w0_packed, w1_packed, shift0, shift1, x_cstride, x0_coff, x1_coff, B, H, W, cin, flags, dtype)) return rc;
-  RD_REQUIRE(head_w0_packed && head_w1_packed && head_bias0 && head_bias1 && out0 && out1, RD_EINVAL, "conv2d_head_out_pair: null pointer");
-  RD_REQUIRE(nout0 >= 1 && nout0 <= 8 && nout1 >= 1 && nout1 <= 8, RD_ESHAPE, "conv2d_head_out_pair: nout %d / %d (1..8)", nout0, nout1);
-  allow_conv_lds();
-  Conv3Args h;
-  memset(&h, 0, sizeof(h));
-  h.hw = (const unsigned char*)head_w0_packed; h.hb = head_bias0; h.ho = out0; h.ho_bs = out0_batch_stride; h.ho_off = n_off; h.hn = nout0;
-  Conv3Second g;
-  memset(&g, 0, sizeof(g));
-  g.x = x1; g.x_co = x1_coff; g.w = w1_packed; g.shift = shift1;
-  g.hw = head_w1_packed; g.hb = head_bias1; g.ho = out1; g.ho_bs = out1_batch_stride; g.hn = nout1;
-  return launch_conv3(x0, x_cstride, x0_coff, w0_packed, nullptr, shift0, nullptr, 0, 0, nullptr, 128, 0, B, H, W, cin, 128, flags, 1,
-                      (hipStream_t)stream, 0, &h, dtype, &g);
+                      (hipStream_t)stream, 0, &h, dtype, nullptr, nullptr, m16 ? C3_BODY_M16 : 0);
 }
 
 int rd_deconv2d_bn_act(const void* x, int x_cstride, int x_coff, const void* w_packed_phase, const float* scale,
@@ -565,7 +518,7 @@ int rd_deconv2d_bn_act_all(const void* x, int x_cstride, int x_coff, const void*
   for (int p = 0; p < stride_w; ++p)
     if (deconv_tap_set(deconv_taps_sorted(kh, kw, stride_w, pad_w, p)) == 2) ph.ts_mask |= 1 << p;
   return launch_conv3(x, x_cstride, x_coff, w_packed_all, nullptr, shift, residual, r_cstride * stride_w, r_coff, y, y_cstride * stride_w,
-                      y_coff, B, H, Win, cin, cout, flags, 1, (hipStream_t)stream, 3, nullptr, dtype, nullptr, &ph);
+                      y_coff, B, H, Win, cin, cout, flags, 1, (hipStream_t)stream, 3, nullptr, dtype, &ph);
 }
 
 // ---- phase PAIRS of a transposed conv (cout 64, stride 4: dla_backbone.py:117-127 agg1) ----------------------------------------
@@ -615,7 +568,7 @@ int rd_deconv2d_bn_act_pairs(const void* x, int x_cstride, int x_coff, const voi
   for (int p = 0; p < stride_w; p += 2)
     if (deconv_tap_set(deconv_taps_sorted(kh, kw, stride_w, pad_w, p)) == 2) ph.ts_mask |= 1 << (p / 2);
   return launch_conv3(x, x_cstride, x_coff, w_packed_pairs, nullptr, shift2, residual, r_cstride * stride_w, r_coff, y, y_cstride * stride_w,
-                      y_coff, B, H, Win, cin, 2 * cout, flags, 1, (hipStream_t)stream, 3, nullptr, dtype, nullptr, &ph);
+                      y_coff, B, H, Win, cin, 2 * cout, flags, 1, (hipStream_t)stream, 3, nullptr, dtype, &ph);
 }
 
 int rd_head_out(const void* x, int x_cstride, int x_coff, const float* w, const float* bias, float* out,
@@ -835,8 +788,8 @@ int rd_wnms_4c_batched(const float* dets, long dets_bstride, int Kcap, const int
   const bool two = Kcap >= 4 * R1 && !one_round;
   // pair tiles are strided over a fixed number of single-wave workgroups per frame: one tile each at the pipeline's typical K
   // (1 - 2 k rows: <= 2048 tiles per round), grid-strided beyond that -- so the launch size does not grow with the capacity
-  const int ct = dev_switches().wnms_ct == 32 ? 32 : dev_switches().wnms_ct == 16 ? 16 : 8;   // columns per pair tile
-  const int pgrid = std::min(2048, std::max(64, nb * (64 / ct) * std::min(nb, 16)));
+  // (8 columns per pair tile, k_wnms.h: 8 tiles per mask word)
+  const int pgrid = std::min(2048, std::max(64, nb * 8 * std::min(nb, 16)));
   // the rejection test of the pair kernel (k_wnms.h w_pair_skippable) is only sound for thresholds far above the noise the
   // reference's clipper returns on disjoint boxes (<= 4.2e-7 inside the test's domain, profiles/r04_nms_spurious_study.txt), and it
   // was characterised on the BEV value only: in 3-D mode the reference divides the clipped area x height overlap by a volume sum
@@ -844,9 +797,7 @@ int rd_wnms_4c_batched(const float* dets, long dets_bstride, int Kcap, const int
   // RD_WNMS_DIAG_NO_SKIP (per call; dev builds also RD_WNMS_NO_SKIP): every pair clipped (A/B)
   const int allow_skip = thresh >= 1e-3f && thresh_vote >= 1e-3f && !is3d && !dev_switches().wnms_no_skip && !(diag & RD_WNMS_DIAG_NO_SKIP);
   auto pairs = [&](const int* rows, const int* nrows, const unsigned long long* supp, int rb_end) {
-    auto k = dev_switches().wnms_bal ? (ct == 8 ? wnms_pairs_kernel<8, true> : ct == 16 ? wnms_pairs_kernel<16, true> : wnms_pairs_kernel<32, true>)
-                                     : (ct == 8 ? wnms_pairs_kernel<8, false> : ct == 16 ? wnms_pairs_kernel<16, false> : wnms_pairs_kernel<32, false>);
-    hipLaunchKernelGGL(k, dim3(pgrid, 1, B), dim3(64), 0, st, w.prep, Kcap, d_count, thresh, thresh_vote, is3d, w.thr, w.vote,
+    hipLaunchKernelGGL(wnms_pairs_kernel, dim3(pgrid, 1, B), dim3(64), 0, st, w.prep, Kcap, d_count, thresh, thresh_vote, is3d, w.thr, w.vote,
                        w.nwcap, bs, rows, nrows, supp, 0, rb_end, allow_skip);
   };
   pairs(nullptr, nullptr, nullptr, two ? nb1 : nb);

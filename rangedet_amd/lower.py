@@ -58,12 +58,11 @@ class Plan:
 
 
 def conv_steps(steps):
-    """The conv / deconv steps of a plan one by one: the two members of a "conv_pair" (one launch) as two entries.
-    Likewise the two convs of a fused BasicBlock ("block").
-    Yields (step, launches): launches = what the step adds to the launch count (1, 0.5 + 0.5 for a pair; a transposed conv: 1 when
+    """The conv / deconv steps of a plan one by one: the two convs of a fused BasicBlock ("block", one launch) as two entries.
+    Yields (step, launches): launches = what the step adds to the launch count (1, 0.5 + 0.5 for a block; a transposed conv: 1 when
     all its phases run in one launch, else stride_w)."""
     for st in steps:
-        if st["kind"] in ("conv_pair", "block"):   # (a fused BasicBlock: its two convs, one launch)
+        if st["kind"] == "block":   # (a fused BasicBlock: its two convs, one launch)
             yield st["a"], 0.5
             yield st["b"], 0.5
         elif st["kind"] == "conv":
@@ -101,7 +100,6 @@ class Lowering:
             self.plan.outputs.append(self.emit_value(out))
         self._fuse_head_out()
         self._fuse_blocks()
-        self._pair_equal_convs()
         self._mark_mfma16()
 
     # ---- fusion ------------------------------------------------------------------------------------------------
@@ -125,77 +123,6 @@ class Lowering:
                 cin = len(st["cmap"]) if st.get("cmap") else st["cin"]
                 if cin % 32 == 0 and cin >= 32:
                     st["m16"] = True
-
-    def _pair_equal_convs(self):
-        """16-bit: two 3x3 convs of the SAME shape whose inputs are both ready run as ONE launch (rd_conv3x3_bn_act_pair /
-        rd_conv2d_bn_act_head_out_pair) -- in this graph the cls and the reg tower conv i of every head level
-        (builder.py:221-240: the towers are built one after the other, layer i of both only depends on layer i-1 of its own
-        tower).  The later conv moves up to the earlier one's place in the plan; it may only do so when the tensor it reads was
-        written before that place.  Plan step kind "conv_pair": a / b = the two conv steps as they were."""
-        # OFF by default (RD_PAIR=1 turns it on, RD_PAIR_MAXW limits it to narrow levels).  Measured on one box, DESIGN.md 6.4: serial on
-        # one stream a pair is 10 % faster than its two launches at W = 664, equal at W = 1328, 2 - 7 % slower at W = 2656 (real
-        # activations); end to end +0.65 % with one batch in flight, -0.4 .. -0.7 % with the default two (the other stream's launches
-        # already fill the tail rounds, and finer launches interleave better).
-        if not self.h16 or devswitch.get("RD_PAIR", "0") in ("", "0"):
-            return
-        max_w = int(devswitch.get("RD_PAIR_MAXW", "100000"))
-        same_input_only = devswitch.get("RD_PAIR", "0") == "2"    # (round 6 experiment: only the tower convs that read the SAME tensor -- conv_0 of a level)
-
-        def sig(st):
-            if st["kind"] != "conv" or not st.get("ex") or not st.get("fold") or st.get("sc") or st.get("s2view") or st.get("x2") is not None:
-                return None
-            if st["res"] is not None or st["cout"] != 128 or st["stride_w"] != 1 or tuple(st["k"]) != (3, 3) or st["flags"] != RD_RELU_POST:
-                return None
-            x, o, h = st["x"], st["out"], st.get("head")
-            if x.W > max_w:
-                return None
-            return (x.H, x.W, x.cs, len(st["cmap"]) if st.get("cmap") else st["cin"], o.cs if not h else None,
-                    (h["n_off"], h["N"]) if h else None)
-
-        def is_write(key):
-            return key in ("out", "out1", "head_out", "head_out1", "keep") or key.startswith("out_")
-
-        out, written, touched, open_ = [], {}, {}, {}
-        for st in self.plan.steps:
-            k = sig(st)
-            if k is not None:
-                # the tensor it reads was written before place j, and nothing from place j on touches what it writes
-                ready = written.get(st["x"].buf, -1)
-                clear = max((touched.get(v.buf, -1) for v in (st["out"], st.get("head_out")) if v is not None), default=-1)
-                j = next((j for j in open_.get(k, []) if ready < j and clear < j and (not same_input_only or out[j]["x"] == st["x"])), None)
-                if j is not None:
-                    open_[k].remove(j)
-                    a = out[j]
-                    p = dict(kind="conv_pair", name=a["name"] + " + " + st["name"], a=a, b=st, x=a["x"], x1=st["x"], out=a["out"],
-                             out1=st["out"])
-                    if a.get("head"):
-                        p["head_out"], p["head_out1"] = a["head_out"], st["head_out"]
-                    out[j] = p
-                    for v in (st["out"], st.get("head_out")):
-                        if v is not None:
-                            written[v.buf] = max(written.get(v.buf, -1), j)
-                            touched[v.buf] = max(touched.get(v.buf, -1), j)
-                    touched[st["x"].buf] = max(touched.get(st["x"].buf, -1), j)
-                    continue
-                open_.setdefault(k, []).append(len(out))
-            def refs(key, v):   # every buffer reference of a step value, also inside lists / tuples / nested dicts
-                if isinstance(v, (TRef, FlatRef)):
-                    yield key, v
-                    if isinstance(v, TRef) and v.tail is not None:
-                        yield key, v.tail
-                elif isinstance(v, dict):
-                    for k2, v2 in v.items():
-                        yield from refs(k2 if isinstance(k2, str) else key, v2)
-                elif isinstance(v, (list, tuple)):
-                    for v2 in v:
-                        yield from refs(key, v2)
-            for key, v in st.items():
-                for k2, r in refs(key, v):
-                    touched[r.buf] = len(out)
-                    if is_write(k2):
-                        written[r.buf] = len(out)
-            out.append(st)
-        self.plan.steps = out
 
     def _fuse_blocks(self):
         """16-bit: a 64-channel BasicBlock at stride 1 (dla_backbone.py:18-56: conv1 3x3 + BN + ReLU -> conv2 3x3 + BN, + shortcut, ReLU)
@@ -513,8 +440,7 @@ class Lowering:
         # columns permuted accordingly (cmap).  RD_CONCAT_BUFFER=1: the shared buffer, for A/B runs.
         acts = [i for i, p in enumerate(parts) if p.op != "var"]
         if self.h16 and len(parts) == 2 and len(acts) == 1 and cs_list[acts[0]] % 32 == 0 and cs_list[1 - acts[0]] <= self.gran and \
-                not devswitch.get("RD_CONCAT_BUFFER") and not devswitch.get("RD_NO_FOLD") and devswitch.get("RD_PAIR", "0") in ("", "0"):
-            # (RD_PAIR=1, the opt-in two-problem tower launches, keeps the shared buffer: that launch form takes one input tensor)
+                not devswitch.get("RD_CONCAT_BUFFER") and not devswitch.get("RD_NO_FOLD"):
             ia, iv = acts[0], 1 - acts[0]
             fa = self.emit_act(parts[ia])
             fv = self.emit_act(parts[iv])

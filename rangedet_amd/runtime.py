@@ -157,9 +157,6 @@ class Executor:
         L, A, dt = self.lib, self.alloc, self.dtype
         k = st["kind"]
         b = dict(st)
-        if k == "conv_pair":
-            b["a"], b["b"] = self._bind(st["a"], P), self._bind(st["b"], P)
-            return b
         if k == "block":   # a fused BasicBlock (lower._fuse_blocks): both 3x3 weights in one image, the shortcut's as for the unfused conv2
             ca, cb = st["a"], st["b"]
             w1, w2 = (np.asarray(P[c["name"] + "_weight"], np.float32) for c in (ca, cb))
@@ -317,24 +314,6 @@ class Executor:
                 else:
                     L.call("rd_block64_bn_act", self.p(x), x.cs, x.co, b["cin"], A.ptr(b["w"]), A.ptr(b["shift1"]), A.ptr(b["shift2"]),
                            A.ptr(b["sc_w"]) if b["sc_w"] is not None else None, self.p(o), o.cs, o.co, B, x.H, x.W, dt, st_)
-            elif k == "conv_pair":
-                # two convs of one shape in ONE launch (lower._pair_equal_convs: the cls and reg tower conv of a head level)
-                p, q = b["a"], b["b"]
-                x0, x1 = p["x"], q["x"]
-                cin = len(p["cmap"]) if p.get("cmap") else p["cin"]
-                if p.get("head"):
-                    h0, h1 = p["head"], q["head"]
-                    L.call("rd_conv2d_bn_act_head_out_pair",
-                           self.p(x0), x0.co, A.ptr(p["w"]), A.ptr(p["shift"]), A.ptr(p["head_w"]), A.ptr(p["head_bias"]),
-                           self.p(h0["out"]), h0["N"] * h0["nout"], h0["nout"],
-                           self.p(x1), x1.co, A.ptr(q["w"]), A.ptr(q["shift"]), A.ptr(q["head_w"]), A.ptr(q["head_bias"]),
-                           self.p(h1["out"]), h1["N"] * h1["nout"], h1["nout"],
-                           x0.cs, h0["n_off"], B, x0.H, x0.W, cin, p["flags"], dt, st_)
-                else:
-                    o0, o1 = p["out"], q["out"]
-                    L.call("rd_conv3x3_bn_act_pair", self.p(x0), x0.co, A.ptr(p["w"]), A.ptr(p["shift"]), self.p(o0), o0.co,
-                           self.p(x1), x1.co, A.ptr(q["w"]), A.ptr(q["shift"]), self.p(o1), o1.co, x0.cs, o0.cs, B, x0.H, x0.W, cin,
-                           p["flags"], dt, st_)
             elif k == "conv" and b.get("head"):
                 x, h = b["x"], b["head"]
                 L.call("rd_conv2d_bn_act_head_out", self.p(x), x.cs, x.co, A.ptr(b["w"]),

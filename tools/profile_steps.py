@@ -37,13 +37,7 @@ for i, st in enumerate(pipe.plan.steps):
     fl = 0.0
     by = 0.0          # bytes THIS launch form has to move (fused form: input once incl. a stride-2 conv's skipped columns, output once,
     desc = ""         # residual / shortcut input once) -- against the HBM roof next to the FLOPs against the MFMA roof
-    if k == "conv_pair":   # two tower convs of one shape in one launch
-        a = st["a"]
-        o = a["out"]
-        fl = 2 * B * 2.0 * o.H * o.W * a["cin"] * a["cout"] * 9
-        by = 2 * B * esz * o.H * o.W * (a["cin"] + (0 if a.get("head") else a["cout"]))
-        desc = "%s %d->%d x2 W%d" % (st["name"].replace("rpn_", "").replace("_conv", ""), a["cin"], a["cout"], o.W)
-    elif k == "block":     # a fused 64-channel BasicBlock: the FLOPs of its two convs (+ the 1x1 shortcut)
+    if k == "block":     # a fused 64-channel BasicBlock: the FLOPs of its two convs (+ the 1x1 shortcut)
         o = st["out"]
         c1 = st["a"]["cin"]
         fl = B * 2.0 * o.H * o.W * 64 * (9 * c1 + 9 * 64 + (c1 if st["b"].get("sc") else 0))
@@ -79,10 +73,6 @@ for i, st in enumerate(pipe.plan.steps):
     if dt in rdlib.H16 and k == "block":
         cus = torch.cuda.get_device_properties(0).multi_processor_count
         ntiles = -(-st["out"].W // 32) * -(-st["out"].H // 8) * B
-        tps = "  %5d tiles / %d slots = %5.2f" % (ntiles, 2 * cus, ntiles / (2 * cus))
-    elif dt in rdlib.H16 and k == "conv_pair":
-        cus = torch.cuda.get_device_properties(0).multi_processor_count
-        ntiles = 2 * -(-st["out"].W // 32) * -(-st["out"].H // 8) * B
         tps = "  %5d tiles / %d slots = %5.2f" % (ntiles, 2 * cus, ntiles / (2 * cus))
     elif dt in rdlib.H16 and k in ("conv", "deconv") and st["k"][0] == 3:
         cus = torch.cuda.get_device_properties(0).multi_processor_count
