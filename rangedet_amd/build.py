@@ -1,7 +1,6 @@
-"""Build librangedet_hip.so (gfx950) in-tree with hipcc.  ``python -m rangedet_amd.build [--force] [--dev]``.
+"""Build librangedet_hip.so (gfx950) in-tree with hipcc.  ``python -m rangedet_amd.build [--force]``.
 
-The default build is the RELEASE library: no development switch, no getenv (csrc/rd_common.h).  ``--dev`` builds
-librangedet_hip_dev.so with -DRD_DEV_SWITCHES next to it (the A/B library of tools/exp/ab.sh: load it with RANGEDET_HIP_LIB=...)."""
+There is one build: the library has no development switch and reads no environment variable."""
 import glob
 import os
 import re
@@ -21,7 +20,6 @@ OUT = os.path.join(HERE, "librangedet_hip.so")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result"]
 CODEGEN_FLAGS = ["-Xarch_device", "-fno-slp-vectorize"]     # (part of source_hash(): they change the device code)
 FLAGS = BASE_FLAGS + CODEGEN_FLAGS
-OUT_DEV = os.path.join(HERE, "librangedet_hip_dev.so")
 
 
 def _hipcc():
@@ -112,14 +110,13 @@ def _stale(out):
     return os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps)
 
 
-def build(force=False, verbose=True, dev=False):
-    """dev=True: librangedet_hip_dev.so with -DRD_DEV_SWITCHES (the environment-driven A/B switches of csrc/rd_common.h)."""
-    out = OUT_DEV if dev else OUT
+def build(force=False, verbose=True):
+    out = OUT
     if not force and not _stale(out):
         return out
     # (a per-process temporary name: several ranks that find the library stale at once must not clobber each other's output)
     tmp_out = "%s.new.%d" % (out, os.getpid())
-    cmd = [_hipcc()] + FLAGS + (["-DRD_DEV_SWITCHES"] if dev else []) + os.environ.get("RD_EXTRA_HIPCC_FLAGS", "").split() + [SRC, "-o", tmp_out]   # e.g. -DRD_CONV3_DEV
+    cmd = [_hipcc()] + FLAGS + os.environ.get("RD_EXTRA_HIPCC_FLAGS", "").split() + [SRC, "-o", tmp_out]
     if verbose:
         print(" ".join(cmd), flush=True)
     try:
@@ -142,4 +139,4 @@ if __name__ == "__main__":
             print(k[:80], "|", ins)
         print("%d packed-fp32 instructions with a swapped second/third source" % len(hits))
         sys.exit(1 if hits else 0)
-    build(force="--force" in sys.argv, dev="--dev" in sys.argv)
+    build(force="--force" in sys.argv)

@@ -757,7 +757,7 @@ inline int launch_block64(const void* x, int x_cs, int x_co, int cin, const void
   a.nslots1 = std::min(2, (x_cs - x_co) / 8);      // (channels past cin are zero in the buffer and meet zero weights)
   a.ncol = (W + 31) / 32; a.nrow = (H + 7) / 8; a.ntiles = a.ncol * a.nrow * B;
   const int grid = std::min(a.ntiles, conv_num_cus() * 2);
-  a.xcd = dev_switches().conv_xcd && (a.ncol * B) % 8 == 0 && grid % 8 == 0;
+  a.xcd = (a.ncol * B) % 8 == 0 && grid % 8 == 0;
   ProfScope ps(RD_PROF_BLOCK, st);
   static std::atomic<unsigned long long> seen{0};
   once_per_device(seen, [] {

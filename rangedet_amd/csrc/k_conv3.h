@@ -308,13 +308,22 @@ inline void pack_body_frag(int BODY, int cin, int cout, void* out, F get, int dt
 // Which body a folded-scale launch on the 8 x 32 tiles takes (the host packers and the launcher must agree): 1 = stride (1,2) on the
 // pixel-pair view whose even / odd halves are whole 128-byte lines (x_cstride a multiple of 64, all of them convolved),
 // 2 = [64 channels | <= 16 channels] (rd_conv3x3_bn_act_cat), 3 = at most 16 input channels, 0 = homogeneous units.
-// RD_CONV_BODY=0 (dev switch, A/B): always 0.
-inline bool conv3_bodies_on() { return dev_switches().conv_body && !dev_switches().conv_v1; }
-inline int conv3_body_s2(int cin, int x_cstride, bool folded) { return folded && conv3_bodies_on() && x_cstride % 64 == 0 && cin == x_cstride ? 1 : 0; }
-inline int conv3_body_small(int cin, bool folded) { return folded && conv3_bodies_on() && cin <= 16 ? 3 : 0; }
-inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && conv3_bodies_on() && cin1 == 64 && cin2 <= 16 ? 2 : 0; }
+inline int conv3_body_s2(int cin, int x_cstride, bool folded) { return folded && x_cstride % 64 == 0 && cin == x_cstride ? 1 : 0; }
+inline int conv3_body_small(int cin, bool folded) { return folded && cin <= 16 ? 3 : 0; }
+inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && cin1 == 64 && cin2 <= 16 ? 2 : 0; }
 // s_waitcnt immediate (gfx9): vmcnt <= vm and lgkmcnt <= lgkm, expcnt untouched
 #define C3_WAIT_IMM(vm, lgkm) (((vm) & 15) | (((vm) >> 4) << 14) | (7 << 4) | ((lgkm) << 8))
+// The vmcnt of every counted wait of the persistent kernel (C3_SYNC).  RD_EMU_CONTROL_NO_COUNTED_WAITS is the negative control of the
+// emulator's late-DMA mode (tools/emu_late_dma_control.py): a HOST-only build in which no wait retires a transfer, so the emulator must
+// report wrong results.  A kernel without its waits is never built for a GPU.
+#ifdef RD_EMU_CONTROL_NO_COUNTED_WAITS
+#ifdef __HIP_DEVICE_COMPILE__
+#error "RD_EMU_CONTROL_NO_COUNTED_WAITS removes the persistent conv's counted waits: emulator (host) builds only"
+#endif
+#define C3_VMCNT(vm) 63
+#else
+#define C3_VMCNT(vm) (vm)
+#endif
 
 // HEAD: the conv is the last layer of a head tower and its only consumer is the tower's 1x1 output conv (<= 8 outputs).
 // That conv is applied to each 32-pixel fragment while it sits, already rounded to bf16, in the epilogue's transpose
@@ -335,13 +344,13 @@ inline int conv3_body_cat(int cin1, int cin2, bool folded) { return folded && co
 // accumulators of 4 registers.  Block 0 = weight fragments 0..3, block 1 = 4..7, pixel-major inside a block, so a pixel half-fragment's
 // register is free after its 4th MFMA of block 1 and is re-read for the next step right there (single buffered); the barrier, the counted
 // waits and the DMA schedule are those of the 32 x 32 form (12 fragment reads per step in both).
-template <int NCT, int DBG = 0, int TS = 0, bool HEAD = false, bool SC = false, bool FOLD = false, C3Tile TILE = C3_8x62,
+template <int NCT, int TS = 0, bool HEAD = false, bool SC = false, bool FOLD = false, C3Tile TILE = C3_8x62,
           int DT = RD_BF16, int BODY = 0, bool M16 = false>
 __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream_kernel(Conv3Args a) {
   using Cfg = C3Cfg<NCT, TILE>;
   constexpr bool WD = Cfg::WIDE;                 // the 8 x 32 tile
   constexpr int FPW = Cfg::FPW, FC = Cfg::FC;    // pixel fragments per wave (4 or 2), per tile row (2 or 1)
-  static_assert(!M16 || (NCT == 4 && WD && FOLD && !SC && TS == 0 && BODY == 0 && DBG == 0),
+  static_assert(!M16 || (NCT == 4 && WD && FOLD && !SC && TS == 0 && BODY == 0),
                 "16 x 16 x 32 form: cout 128 on the 8 x 32 tiles, folded scales, all nine taps");
   static_assert(BODY == 0 || (WD && FOLD && !HEAD && (TS == 0 || TS == 1)), "heterogeneous tile bodies: 8 x 32 tiles, folded scales");
   static_assert(!WD || FOLD, "8 x 32 tile: no room for the scale / shift array");
@@ -515,17 +524,15 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
       asm volatile("" : "+v"(ol));
       const int pp = 16 * q + (ol >> 2), r = (pp * 1928) >> 16, cc = pp - 34 * r;
       const int hsp = (ol & 3) ^ ((cc >> 2) & 3);
-      ok = hsp < hns && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim && pp < Cfg::NPX && !(DBG & 16);
+      ok = hsp < hns && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim && pp < Cfg::NPX;
       src = hbase + (long)((r * a.W + cc) * hpxb + hsp * 16);
     } else {
     const int r = q >> 2, c16 = (q & 3) * 16;
     const int cc = c16 + l4;
-    ok = hsok && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim && !(DBG & 16);
+    ok = hsok && (unsigned)(hh0 + r) < (unsigned)a.H && cc >= hlo && cc < hlim;
     const unsigned char* sp = hbase + ((long)r * a.W + c16) * (long)a.x_cs * 2;
     src = sp + hlane;
     }
-    if constexpr ((DBG & 256) != 0)   // ablation: the same lanes' data from the first MB of x (L2-resident REAL data: MFMA power as in production, no HBM reads)
-      src = (const unsigned char*)a.x + ((size_t)(src - (const unsigned char*)a.x) & 0xFFFF0);
     dma_v(ok ? (const void*)src : (const void*)a.zero16, buf + q * 1024);   // (buf = byte offset of the halo buffer)
   };
   int fslot = 0, fslab = 0;                               // ring slot / slab-within-tile of the NEXT slab to fetch
@@ -588,17 +595,13 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
   // MFMA n of a k-step: pixel fragment n / NCT against channel fragment n % NCT (transposed: weights are operand A)
 #define C3_MM(BUF, N)                                                                                     \
   {                                                                                                       \
-    if (!(DBG & 8))                                                                                       \
-      acc[(N) / NCT][(N) % NCT] = H16<DT>::mfma(fb[BUF][(N) % NCT], fa[BUF][(N) / NCT], \
-                                                                          acc[(N) / NCT][(N) % NCT]);    \
+    acc[(N) / NCT][(N) % NCT] = H16<DT>::mfma(fb[BUF][(N) % NCT], fa[BUF][(N) / NCT], acc[(N) / NCT][(N) % NCT]); \
     C3_FENCE();                                                                                           \
   }
   // first k-step of a tile: C = 0 as an inline constant instead of zeroing 16 * 4 * NCT accumulator registers per tile
 #define C3_MMZ(BUF, N)                                                                                    \
   {                                                                                                       \
-    if (!(DBG & 8))                                                                                       \
-      acc[(N) / NCT][(N) % NCT] = H16<DT>::mfma(fb[BUF][(N) % NCT], fa[BUF][(N) / NCT], \
-                                                                          f32x16{});             \
+    acc[(N) / NCT][(N) % NCT] = H16<DT>::mfma(fb[BUF][(N) % NCT], fa[BUF][(N) / NCT], f32x16{});             \
     C3_FENCE();                                                                                           \
   }
   // M16: weight fragment C of the slab half at BADDR; pixel half-fragment HX = 2*row + half of the tap at AADDR; MFMA N of block BK =
@@ -615,8 +618,8 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
 #define C3_SYNC(VMCNT, LGKM)                                      \
   {                                                               \
     asm volatile("" ::: "memory");                                \
-    __builtin_amdgcn_s_waitcnt(C3_WAIT_IMM((DBG & 32) ? 63 : (VMCNT), LGKM)); \
-    if (!(DBG & 2)) __builtin_amdgcn_s_barrier();                 \
+    __builtin_amdgcn_s_waitcnt(C3_WAIT_IMM(C3_VMCNT(VMCNT), LGKM)); \
+    __builtin_amdgcn_s_barrier();                                 \
     asm volatile("" ::: "memory");                                \
     C3_FENCE();                                                   \
   }
@@ -683,13 +686,12 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     if ((S) == 0) halo_begin();                                                                                      \
     _Pragma("unroll") for (int n = NM / 2; n < NM; ++n) {                                                            \
       C3_MM(1, n)                                                                                                    \
-      if (!(DBG & 4)) {   /* the step's DMA pieces, spread over the MFMA slots of this half block (slab pieces first) */ \
-        _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                              \
-          if (p * (NM / 2) / NP_ == n - NM / 2) {                                                                    \
-            if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                    \
-            C3_FENCE();                                                                                              \
-          }                                                                                                          \
-      }                                                                                                              \
+      /* the step's DMA pieces, spread over the MFMA slots of this half block (slab pieces first) */                 \
+      _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                                \
+        if (p * (NM / 2) / NP_ == n - NM / 2) {                                                                      \
+          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                      \
+          C3_FENCE();                                                                                                \
+        }                                                                                                            \
     }                                                                                                                \
     slab_advance();                                                                                                  \
     rslot = rnext_;                                                                                                  \
@@ -957,11 +959,10 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
       Slot16 rv[2][NCT][2];
       auto res_load = [&](int i, Slot16 (&dst)[NCT][2]) {
         const int tc = 32 * (i % FC) + em, ow = ct * C3_TW + tc, oh = oh0 + i / FC;
-        const bool live = tc < C3_TW && ow < a.W && oh < a.H && !(ow & sh) && !(DBG & 64);   // (DBG 64: every lane reads pixel 0 -- L2 hits)
+        const bool live = tc < C3_TW && ow < a.W && oh < a.H && !(ow & sh);
         const bf16_t* rp = rimg0 + (live ? ((size_t)oh * a.Wo + (size_t)(ow >> sh)) * a.r_cs : 0) + 16 * ehi;
 #pragma unroll
         for (int j = 0; j < NCT; ++j) {
-          if (DBG & 128) { dst[j][0] = Slot16{0, 0, 0, 0}; dst[j][1] = Slot16{0, 0, 0, 0}; continue; }   // (DBG 128: no residual load)
           dst[j][0] = *(const Slot16*)(rp + j * 32);
           dst[j][1] = *(const Slot16*)(rp + j * 32 + 8);
         }
@@ -1078,7 +1079,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
             const int pr = it * RPI + el / SPR, sl = el % SPR;
             const Slot16 v = *(const Slot16*)(scr + pr * ROWB + ((sl ^ (pr & (SPR - 1))) << 4));
             const int tcs = 32 * (i % FC) + pr, ows = ct * C3_TW + tcs;
-            if (tcs < C3_TW && ows < a.W && oh0 + i / FC < a.H && !(ows & sh) && (!(DBG & 1) || a.B < 0))
+            if (tcs < C3_TW && ows < a.W && oh0 + i / FC < a.H && !(ows & sh))
               // non-temporal: an output line is written once and read back by the NEXT launch; without the hint the stores displace the
               // halo rows / residual lines that neighbouring tiles are about to re-read (A/B on one box, 7 alternations: +0.7 ... +0.9 %
               // frames/s, serial step sum -2.5 ... -3.3 %; a run-time size test around the store gave the gain away again, EXPERIMENTS.md)
@@ -1259,7 +1260,7 @@ inline int conv_num_cus() {
 // One launch of one instantiation; the first launch of each raises its dynamic-LDS limit (once per process and instantiation).
 template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, C3Tile TILE, int DT, int BODY = 0, bool M16 = false>
 inline int c3_go(int grid, hipStream_t st, const Conv3Args& a) {
-  auto k = conv3x3_stream_kernel<NCT, 0, TS, HEAD, SC, FOLD, TILE, DT, BODY, M16>;
+  auto k = conv3x3_stream_kernel<NCT, TS, HEAD, SC, FOLD, TILE, DT, BODY, M16>;
   static std::atomic<unsigned long long> seen{0};
   once_per_device(seen, [&] { allow_big_lds(k); });
   constexpr size_t lds = C3Cfg<NCT, TILE>::LDS + (HEAD && TILE == C3_8x62 ? 16384 : 0);   // (8 x 62 tile: the output conv's weights in LDS)
@@ -1281,7 +1282,7 @@ inline bool conv3_eligible(const TapList& tl, int in_stride, int out_stride, int
   if (cout != 64 && cout != 128) return false;
   for (int t = 0; t < 9; ++t)
     if (tl.dh[t] != t / 3 - 1 || tl.dw[t] != t % 3 - 1) return false;
-  return !dev_switches().conv_v1;
+  return true;
 }
 
 // All phases of a transposed conv in one launch (PH form, TS = 3): per-phase weight images w + ph * w_pb, tap-set side per phase
@@ -1290,13 +1291,13 @@ struct Conv3Phases { int nph, ts_mask, y_pc, r_pc; long w_pb; };
 // (a multiple of 32) channels come from x
 struct Conv3Src2 { const void* x; int cs, co, cin1, cin2; };
 inline bool conv3_phases_eligible(int cout, int flags) {
-  return (cout == 64 || cout == 128) && (flags & RD_SCALE_FOLDED) && !dev_switches().conv_v1;
+  return (cout == 64 || cout == 128) && (flags & RD_SCALE_FOLDED);
 }
 // Does the launcher have the v_mfma_f32_16x16x32 form (RD_MFMA16) for this conv?  The packer side of the contract: an image made by
 // rd_pack_conv3x3_m16_host may only be launched where this says yes (the launch fails loudly otherwise).
 // (with or without a fused output conv, at any width: an RD_MFMA16 launch always takes the 8 x 32 tile)
 inline bool conv3_mfma16_ok(int cin, int cout, int stride_w) {
-  return cout == 128 && stride_w == 1 && cin >= 32 && cin % 32 == 0 && !dev_switches().conv_v1;
+  return cout == 128 && stride_w == 1 && cin >= 32 && cin % 32 == 0;
 }
 
 template <int DT>
@@ -1357,27 +1358,9 @@ inline int launch_conv3_dt(const void* x, int x_cs, int x_co, const void* w, con
     a.nchunk1 = s2->cin1 / 32; a.nslots2 = cin_slots(s2->cin2, RD_BF16); a.nslots = a.nchunk1 * 4;
   }
   const int grid = std::min(a.ntiles, conv_num_cus() * (wide ? 2 : 1));
-  a.xcd = dev_switches().conv_xcd && (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
+  a.xcd = (a.ncol * B) % 8 == 0 && grid % 8 == 0;   // (a pure permutation of the tile list under these conditions)
   if (conv_trace_buf() && (size_t)grid * 8 <= (1u << 20)) a.trace = conv_trace_buf();
   ProfScope ps(RD_PROF_CONV3, st);
-#ifdef RD_CONV3_DEV   // ablation variants (bf16; DBG bits: 2 no barrier, 4 no DMA after the prologue, 16 halo from the zero page, 32 no vmcnt wait)
-  static const int dbg = getenv("RD_CONV3_DBG") ? atoi(getenv("RD_CONV3_DBG")) : 0;
-  // plain cout-128 conv with un-folded scales on the 8 x 62 tile
-#define C3_DBG_CASE(D) if (cout == 128 && !fold && !head && ts == 0 && DT == RD_BF16 && dbg == D) { auto k = conv3x3_stream_kernel<4, D>; allow_big_lds(k); hipLaunchKernelGGL(k, dim3(grid), dim3(256), C3Cfg<4>::LDS, st, a); return check_launch("conv3x3_stream_kernel<dbg>"); }
-  C3_DBG_CASE(2) C3_DBG_CASE(4) C3_DBG_CASE(16) C3_DBG_CASE(32)
-#undef C3_DBG_CASE
-  // plain conv with folded scales on the 8 x 32 tile, cout 32 * N: (also) 8 no MFMAs, 64 residual from one L2-resident pixel, 128 no residual
-  // load, 256 halo from the first MB of x (L2-resident REAL data), 1 no stores
-#define C3_DBG(N, D)                                                                                                    \
-  if (cout == 32 * N && wide && !head && !ph && !s2 && !body && sw == 1 && ts == 0 && DT == RD_BF16 && dbg == D) { \
-    auto k = conv3x3_stream_kernel<N, D, 0, false, false, true, C3_8x32>; allow_big_lds(k);                             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), (C3Cfg<N, C3_8x32>::LDS), st, a);                                      \
-    return check_launch("conv3x3_stream_kernel<dbg>");                                                                  \
-  }
-  C3_DBG(2, 4) C3_DBG(2, 8) C3_DBG(2, 16) C3_DBG(2, 64) C3_DBG(2, 128) C3_DBG(2, 256) C3_DBG(2, 257)
-  C3_DBG(4, 4) C3_DBG(4, 8) C3_DBG(4, 16) C3_DBG(4, 2) C3_DBG(4, 32) C3_DBG(4, 256) C3_DBG(4, 257)
-#undef C3_DBG
-#endif
 #ifdef RD_CONV3_DEV_M16_ONLY   // tools/micro/conv16_dev.hip: only the plain cout-128 form on the 8 x 32 tiles, in its two MFMA shapes (a one-minute build)
   RD_REQUIRE(wide && !sc && !ph && !s2 && sw == 1 && ts == 0 && cout == 128 && DT == RD_BF16 && (!headfuse || body == C3_BODY_M16), RD_ESHAPE, "conv16_dev: plain bf16 cout-128 form only");
   if (body == C3_BODY_M16 && headfuse) return c3_go<4, 0, true, false, true, C3_8x32, RD_BF16, 0, true>(grid, st, a);

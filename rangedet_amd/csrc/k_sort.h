@@ -336,10 +336,9 @@ inline int radix_sort_pairs(const SortWs& s, long N, hipStream_t st, int nb = 1,
 
 // the k smallest (key, index) pairs of keysA / idxA, sorted: in *rk / *ri (one of the two buffer pairs; positions >= k unspecified)
 inline int radix_topk_pairs(const SortWs& s, long N, long k, hipStream_t st, int nb, long ws_stride, unsigned** rk, unsigned** ri) {
-  const bool off = dev_switches().sort_no_select;      // dev switch
   *rk = s.keysA; *ri = s.idxA;
   RD_REQUIRE(k > 0 && k <= N, RD_ESHAPE, "top-k: k %ld of N %ld", k, N);
-  if (off || 2 * k > N) return radix_sort_pairs(s, N, st, nb, ws_stride);
+  if (2 * k > N) return radix_sort_pairs(s, N, st, nb, ws_stride);
   { int rc = sort_clear(s, st, nb, ws_stride, true); if (rc != RD_OK) return rc; }
   hipLaunchKernelGGL(select_hist_kernel, dim3(s.nblk, nb), dim3(256), 0, st, s.keysA, N, s.h12, ws_stride);
   hipLaunchKernelGGL(select_thresh_kernel, dim3(1, nb), dim3(256), 0, st, s.h12, k, s.sel, ws_stride);

@@ -299,7 +299,6 @@ int rd_conv3x3_bn_act_ex(const void* x, int x_cstride, int x_coff, const void* w
   RD_REQUIRE(x_cstride % 8 == 0 && x_coff % 8 == 0 && x_coff + cin_slots(cin, RD_BF16) * 8 <= x_cstride, RD_ESHAPE, "conv3x3_ex: x channel stride/offset");
   RD_REQUIRE(!(sc_x && residual) && !(sc_x && !sc_w_packed), RD_EINVAL, "conv3x3_ex: shortcut conv and residual are exclusive");
   RD_REQUIRE(!((flags & RD_ADD) && !residual && !sc_x), RD_EINVAL, "conv3x3_ex: RD_ADD without residual / shortcut");
-  RD_REQUIRE(!dev_switches().conv_v1, RD_EINVAL, "conv3x3_ex: needs the persistent 3x3 kernel (RD_CONV_V1 is set)");
   allow_conv_lds();
   const int v = stride_w;                      // pixels per view pixel
   const int Wv = Win / v;
@@ -406,7 +405,6 @@ int rd_conv3x3_bn_act_cat(const void* x1, int x1_cstride, int x1_coff, int cin1,
   RD_REQUIRE(y_coff >= 0 && y_coff + cout <= y_cstride, RD_ESHAPE, "conv3x3_cat: y channels exceed stride");
   RD_REQUIRE(x1_cstride % 8 == 0 && x1_coff % 8 == 0 && x1_coff + cin1 <= x1_cstride && x2_cstride % 8 == 0 && x2_coff % 8 == 0 &&
              x2_coff + cin2 <= x2_cstride, RD_ESHAPE, "conv3x3_cat: channel stride/offset");
-  RD_REQUIRE(!dev_switches().conv_v1, RD_ESHAPE, "conv3x3_cat: needs the persistent 3x3 kernel (RD_CONV_V1 is set)");
   allow_conv_lds();
   Conv3Src2 s2;
   s2.x = x2; s2.cs = x2_cstride; s2.co = x2_coff; s2.cin1 = cin1; s2.cin2 = cin2;
@@ -442,7 +440,6 @@ int rd_conv2d_bn_act_head_out(const void* x, int x_cstride, int x_coff, const vo
   RD_REQUIRE(!(flags & RD_ADD), RD_EINVAL, "conv2d_head_out: no residual in a head tower");
   RD_REQUIRE(x_cstride % 8 == 0 && x_coff % 8 == 0 && x_coff + cin_slots(cin, RD_BF16) * 8 <= x_cstride, RD_ESHAPE,
              "conv2d_head_out: x channel stride/offset");
-  RD_REQUIRE(!dev_switches().conv_v1, RD_EINVAL, "conv2d_head_out: needs the persistent 3x3 kernel (RD_CONV_V1 is set)");
   RD_REQUIRE(!conv3_body_small(cin, (flags & RD_SCALE_FOLDED) != 0), RD_ESHAPE, "conv2d_head_out: cin %d (the packed image of a conv with <= 16 input channels is not this launch form's)", cin);
   const bool m16 = (flags & RD_MFMA16) != 0;
   RD_REQUIRE(!m16 || ((flags & RD_SCALE_FOLDED) && conv3_mfma16_ok(cin, 128, 1)), RD_ESHAPE,
@@ -472,7 +469,7 @@ int rd_deconv2d_bn_act(const void* x, int x_cstride, int x_coff, const void* w_p
   if (deconv_embeds_3x3(tl)) {
     const int ts = deconv_tap_set(tl);
     if (!ts) tl = conv_taps(3, 3);   // packed as a full 3x3 window with zero weights (rd_pack_deconv_weight_host)
-    if (is_h16(dtype) && Wout == stride_w * Win && (cout == 64 || cout == 128) && !dev_switches().conv_v1 &&
+    if (is_h16(dtype) && Wout == stride_w * Win && (cout == 64 || cout == 128) &&
         conv3_has_form(dtype, (flags & RD_SCALE_FOLDED) != 0)) {
       // phase pixels of the output seen as [H][Win][stride_w * Cstride]: channel offset phase * Cstride
       const bf16_t* r = (const bf16_t*)residual;
@@ -632,7 +629,7 @@ int rd_meta_kernel_fwd(const void* data, int d_cstride, int d_coff, const float*
     once_per_device(seen, [] { allow_big_lds(meta16_kernel<WAVES, RD_BF16>); allow_big_lds(meta16_kernel<WAVES, RD_F16>); });
     const dim3 mgrid(std::min(a.ntiles, conv_num_cus())), mblock(WAVES * 64);
     const int strips = a.tiles_w * B;
-    a.r0 = dev_switches().conv_xcd && strips % 8 == 0 ? 8 : strips;   // (MetaArgs::r0: XCD-aware tile order; a permutation for any grid)
+    a.r0 = strips % 8 == 0 ? 8 : strips;   // (MetaArgs::r0: XCD-aware tile order; a permutation for any grid)
     RD_REQUIRE((unsigned long long)a.ntiles * (unsigned)std::max(a.r0, std::max(a.tiles_h, a.tiles_w)) < (1ull << 32), RD_ESHAPE,
                "meta_kernel: %d tiles exceed the range of the tile decode", a.ntiles);
     a.m0 = meta_magic(a.r0); a.m1 = meta_magic(a.tiles_h); a.m2 = meta_magic(a.tiles_w);
@@ -784,8 +781,7 @@ int rd_wnms_4c_batched(const float* dets, long dets_bstride, int Kcap, const int
   // only for the later rows that are still unsuppressed (compacted list) and resumes the scan.  Results are identical
   // to the one-round form -- the skipped rows are exactly the ones whose bits nobody reads.
   const int R1 = 256, nb1 = R1 / 64;
-  const bool one_round = dev_switches().wnms_one_round;   // dev switch (tools/wnms_bench.py)
-  const bool two = Kcap >= 4 * R1 && !one_round;
+  const bool two = Kcap >= 4 * R1;
   // pair tiles are strided over a fixed number of single-wave workgroups per frame: one tile each at the pipeline's typical K
   // (1 - 2 k rows: <= 2048 tiles per round), grid-strided beyond that -- so the launch size does not grow with the capacity
   // (8 columns per pair tile, k_wnms.h: 8 tiles per mask word)
@@ -794,15 +790,15 @@ int rd_wnms_4c_batched(const float* dets, long dets_bstride, int Kcap, const int
   // reference's clipper returns on disjoint boxes (<= 4.2e-7 inside the test's domain, profiles/r04_nms_spurious_study.txt), and it
   // was characterised on the BEV value only: in 3-D mode the reference divides the clipped area x height overlap by a volume sum
   // that non-positive or cancelling heights can make arbitrarily small (nms.h:234-246), so there every pair is clipped.
-  // RD_WNMS_DIAG_NO_SKIP (per call; dev builds also RD_WNMS_NO_SKIP): every pair clipped (A/B)
-  const int allow_skip = thresh >= 1e-3f && thresh_vote >= 1e-3f && !is3d && !dev_switches().wnms_no_skip && !(diag & RD_WNMS_DIAG_NO_SKIP);
+  // RD_WNMS_DIAG_NO_SKIP (per call): every pair clipped (A/B)
+  const int allow_skip = thresh >= 1e-3f && thresh_vote >= 1e-3f && !is3d && !(diag & RD_WNMS_DIAG_NO_SKIP);
   auto pairs = [&](const int* rows, const int* nrows, const unsigned long long* supp, int rb_end) {
     hipLaunchKernelGGL(wnms_pairs_kernel, dim3(pgrid, 1, B), dim3(64), 0, st, w.prep, Kcap, d_count, thresh, thresh_vote, is3d, w.thr, w.vote,
                        w.nwcap, bs, rows, nrows, supp, 0, rb_end, allow_skip);
   };
   pairs(nullptr, nullptr, nullptr, two ? nb1 : nb);
-  // capacities up to 8 192 rows: the four-wave scan with grouped staging (RD_WNMS_SCAN1 / a forced tile width: the single-wave form)
-  const bool scan4 = w.nwcap <= 128 && !e_tw && !dev_switches().wnms_scan1;
+  // capacities up to 8 192 rows: the four-wave scan with grouped staging (a forced tile width: the single-wave form)
+  const bool scan4 = w.nwcap <= 128 && !e_tw;
   const int tile_words = 64 * 128;
   const size_t scan4_lds = ((size_t)w.nwcap + tile_words) * 8;
   auto scan = [&](int c_begin, int c_end, unsigned long long* state) {

@@ -2,8 +2,7 @@
 
 A release process takes none of them: what gets fused or folded does not depend on the environment of whoever started the
 process.  With RD_DEV_SWITCHES=1 in the environment the historical variables (RD_NO_FUSE_BLOCK, RD_CONCAT_BUFFER, ... -- DESIGN.md
-section 9) are honoured again, for A/B runs of one change on one box.  The native library follows the same rule at build time
-(-DRD_DEV_SWITCHES, csrc/rd_common.h)."""
+section 9) are honoured again, for A/B runs of one change on one box.  The native library has no switches at all."""
 import os
 
 

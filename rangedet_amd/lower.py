@@ -160,7 +160,7 @@ class Lowering:
                     st.get("fold") and not st.get("head") and st.get("x2") is None and st["x"].tail is None):
                 return False
             if first and st["x"].cs - st["x"].co == 16 and st["x"].C <= 16:
-                return not devswitch.get("RD_NO_FUSE_FIRST")      # (A/B switch: keep the first block as two launches)
+                return True
             return st["cin"] == 64 and st["x"].C == 64 and not st.get("cmap")
 
         out, i = [], 0
@@ -191,7 +191,7 @@ class Lowering:
         """bf16: the last conv of a head tower whose ONLY consumer is one 1x1 output conv (rpn_cls_logit / rpn_reg_delta of a
         single-class head) runs as rd_conv2d_bn_act_head_out: the output conv is applied in the 3x3 kernel's epilogue and the
         128-channel tower output is never written to HBM nor read back.  (Two classes read the tensor twice: left alone.)"""
-        if not self.h16 or devswitch.get("RD_NO_FUSE_HEAD"):
+        if not self.h16:
             return
         steps = self.plan.steps
         uses = {}
@@ -333,9 +333,9 @@ class Lowering:
             raise NotImplementedError("Convolution %s: %d output channels inside a channel concat (only 64 / 128 there)" % (conv.name, cout_l))
         out = self._out(cout, x.H, Wout, dest) if cout == cout_l else self.new_act(cout_l, x.H, Wout, cs=cout)
         # extended 3x3 entry (bf16): stride (1,2) on the pixel-pair view (even width), and / or the fused projection shortcut
-        # and, unless RD_NO_FOLD is set, every bf16 3x3 conv with the BatchNorm scale folded into its weights (RD_SCALE_FOLDED)
-        fold = self.h16 and k == (3, 3) and not devswitch.get("RD_NO_FOLD")
-        s2view = sw == 2 and x.W % 2 == 0 and not devswitch.get("RD_NO_S2_VIEW")
+        # and every bf16 3x3 conv with the BatchNorm scale folded into its weights (RD_SCALE_FOLDED)
+        fold = self.h16 and k == (3, 3)
+        s2view = sw == 2 and x.W % 2 == 0
         ex = self.h16 and k == (3, 3) and (sc is not None or s2view or (fold and sw == 1))
         kw_fold = dict(fold=bool(ex and (fold or sc is not None)), s2view=bool(ex and s2view))
         kw = {}
@@ -353,7 +353,7 @@ class Lowering:
     def _fusable_projection(self, main_conv, sc):
         """sc = BN(Convolution 1x1, no bias) with the main 3x3 conv's stride, at most 128 input channels, and (stride 2) an even
         input width: the shortcut the persistent 3x3 kernel can accumulate in its epilogue (bf16 only)."""
-        if not self.h16 or devswitch.get("RD_NO_FUSE_SC"):
+        if not self.h16:
             return None
         if not (sc.op == "BatchNorm" and sc.inputs[0].op == "Convolution"):
             return None
@@ -403,10 +403,10 @@ class Lowering:
                 out = self._out(cout, x.H, Wout, dest) if cout == cout_l else self.new_act(cout_l, x.H, Wout, cs=cout)
                 if (res.C, res.H, res.W) != (cout_l, x.H, Wout) or (cout != cout_l and (res.cs != cout or res.co != 0)):
                     raise ValueError("agg add shape mismatch at %s" % add.name)
-                fold = self.h16 and cout in (64, 128) and not devswitch.get("RD_NO_FOLD")
+                fold = self.h16 and cout in (64, 128)
                 # every phase a 3 x 2 tap set (kw = 2 sw, pad = sw / 2: k(3,8) s4 p2, k(3,4) s2 p1): all phases in ONE launch
                 # (rd_deconv2d_bn_act_all; the executor checks this against rd_deconv2d_all_phases_ok)
-                one = bool(fold and kw == 2 * sw and 2 * pw == sw and not devswitch.get("RD_DECONV_PER_PHASE"))
+                one = bool(fold and kw == 2 * sw and 2 * pw == sw)
                 self.step("deconv", name=dc.name, bn=bn.name, eps=bn.attrs["eps"], x=x, out=out, res=res, cin=x.C,
                           cout=cout, cout_logical=cout_l, k=(kh, kw), stride_w=sw, pad_w=pw, flags=RD_RELU_PRE | RD_ADD, fold=fold, one_launch=one)
                 return out
@@ -440,7 +440,7 @@ class Lowering:
         # columns permuted accordingly (cmap).  RD_CONCAT_BUFFER=1: the shared buffer, for A/B runs.
         acts = [i for i, p in enumerate(parts) if p.op != "var"]
         if self.h16 and len(parts) == 2 and len(acts) == 1 and cs_list[acts[0]] % 32 == 0 and cs_list[1 - acts[0]] <= self.gran and \
-                not devswitch.get("RD_CONCAT_BUFFER") and not devswitch.get("RD_NO_FOLD"):
+                not devswitch.get("RD_CONCAT_BUFFER"):
             ia, iv = acts[0], 1 - acts[0]
             fa = self.emit_act(parts[ia])
             fv = self.emit_act(parts[iv])

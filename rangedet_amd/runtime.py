@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from . import devswitch, lib as rdlib
+from . import lib as rdlib
 from .lower import FlatRef, TRef
 
 
@@ -236,17 +236,16 @@ class Executor:
             fs = s if st.get("fold") else None
             imgs = [L.pack_deconv_weight(w, st["stride_w"], st["pad_w"], ph, dt, fold_scale=fs) for ph in range(st["stride_w"])]
             # all phases in ONE launch when the library has that form for this layer (16-bit, folded scale, 3 x 2 phases):
-            # the phase images back to back in one buffer (RD_DECONV_PER_PHASE=1: one launch per phase, for A/B runs)
+            # the phase images back to back in one buffer
             b["all_phases"] = bool(st.get("one_launch")) and len({len(i) for i in imgs}) == 1 and \
                 L.raw("rd_deconv2d_all_phases_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt) == 1
             if st.get("one_launch") and not b["all_phases"] and not L.raw("rd_deconv2d_all_phases_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt):
-                b["one_launch"] = False      # (a development switch turned the library's form off: per-phase launches)
+                b["one_launch"] = False      # (the library has no such form for this layer: per-phase launches)
             if b["all_phases"]:
                 b["w_all"], b["w_pb"] = A.upload(np.concatenate(imgs)), len(imgs[0])
-            # phases 2p | 2p+1 as one 128-channel problem where the layer has that form and its tensors are dense (agg1: 128 -> 64, stride 4;
-            # RD_DECONV_NO_PAIRS=1: the all-phases launch, for A/B runs)
+            # phases 2p | 2p+1 as one 128-channel problem where the layer has that form and its tensors are dense (agg1: 128 -> 64, stride 4)
             r_, o_ = st["res"], st["out"]
-            b["pairs"] = b["all_phases"] and not devswitch.get("RD_DECONV_NO_PAIRS") and o_.cs == st["cout"] and o_.co == 0 and \
+            b["pairs"] = b["all_phases"] and o_.cs == st["cout"] and o_.co == 0 and \
                 (r_ is None or (r_.cs == st["cout"] and r_.co == 0)) and \
                 L.raw("rd_deconv2d_phase_pairs_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt) == 1
             if b["pairs"]:

@@ -42,9 +42,9 @@ def test_product_library_loads_and_exports_every_symbol():
 
 
 def test_release_library_reads_no_environment():
-    """Round 6: the shipped library's code paths do not depend on the environment of the process -- the development
-    switches are compile-time constants unless built with -DRD_DEV_SWITCHES (csrc/rd_common.h), and the Python-side lowering switches are
-    ignored unless RD_DEV_SWITCHES=1 (rangedet_amd/devswitch.py).  Checked on the binary: it does not even import getenv."""
+    """Round 6: the library's code paths do not depend on the environment of the process -- it has no development
+    switches and only one build -- and the Python-side lowering switches are ignored unless RD_DEV_SWITCHES=1 (rangedet_amd/devswitch.py).
+    Checked on the binary: it does not even import getenv."""
     import subprocess
     from rangedet_amd import build, devswitch
     path = build.build(verbose=False)

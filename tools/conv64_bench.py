@@ -1,10 +1,7 @@
 """The HBM-bound 64->64 3x3 layers through the PRODUCTION entry point (rd_conv3x3_bn_act_ex, folded scales, 8 x 32 tiles): us,
-TFLOP/s and TB/s of algorithmic bytes, with and without the residual.  Tuning aid; the ablation switch RD_CONV3_DBG
-of a -DRD_CONV3_DEV build selected through RANGEDET_HIP_LIB is read by the library.
+TFLOP/s and TB/s of algorithmic bytes, with and without the residual.  Tuning aid (RANGEDET_HIP_LIB selects another build of the library).
     [B=8] [WS=2656,1328] [C128=1] [RES=0|1|both] [ITER=30] python tools/conv64_bench.py
 (RES / ITER / WS select ONE launch class for a counter pass: tools/pmc_conv_classes.sh)
-(Round 6: the RD_* variables named here are DEVELOPMENT switches -- the release library ignores them.  Build the A/B library with
-`python -m rangedet_amd.build --dev` and run with RANGEDET_HIP_LIB=rangedet_amd/librangedet_hip_dev.so RD_DEV_SWITCHES=1; tools/exp/ab.sh does both.)
 """
 import os
 import sys
@@ -21,7 +18,7 @@ H = 64
 B = int(os.environ.get("B", "8"))
 st = torch.cuda.current_stream().cuda_stream
 DT = R.RD_F16 if os.environ.get("F16") else R.RD_BF16
-tag = " ".join("%s=%s" % (k, os.environ[k]) for k in ("RD_CONV3_DBG",) if k in os.environ)
+tag = os.path.basename(os.environ.get("RANGEDET_HIP_LIB", ""))
 for W in [int(v) for v in os.environ.get("WS", "2656,1328").split(",")]:
     for cin, cout in {"1": ((64, 64), (128, 128)), "only": ((128, 128),)}.get(os.environ.get("C128", ""), ((64, 64),)):
         # several distinct buffers cycled so that no launch finds its input in the Infinity Cache by accident of the benchmark
