@@ -17,8 +17,8 @@ Fusions (each replaces an MXNet op chain of the reference by one kernel):
   contrib.NMS3D (wnms=False)                       -> rd_nms3d                                  (builder.py:530-534)
   Custom(batch_rotated_iou, iou_type='bev' | '3d') -> rd_batch_rotated_iou / rd_batch_rotated_iou_3d  (builder.py:176-182)
 Anything that does not match raises NotImplementedError at lowering time -- there is no slow generic path.
+A plan step is a dict; the tensors it holds (TRef / FlatRef, at any depth) are enumerated by step_refs, for every pass that needs them.
 """
-import os
 from dataclasses import dataclass, field
 
 from . import devswitch
@@ -55,6 +55,23 @@ class Plan:
     outputs: list = field(default_factory=list)   # per Group output: ("flat", FlatRef) | ("input", name) | ("zeros", shape)
     input_vars: dict = field(default_factory=dict)  # var name -> shape (without batch) expected from the caller
     num_classes: int = 1
+
+
+def step_refs(step):
+    """Every TRef / FlatRef a plan step holds, at ANY depth, as (key path, reference): nested dicts, lists and tuples (the `a` / `b` convs of a
+    "block", the `sc` and `head` dicts) and the `tail` of a virtual concat.  The one place that knows where a step keeps its tensors: the
+    fusion passes below and the executor's buffer liveness (runtime.Executor._assign_buffers) all read it.  One tensor may come up under
+    several paths of one step (`x2` and `x.tail`, `head_out` and `head.out`, `sc_x` and `b.sc_x`): a pass that counts readers counts steps.
+    Works on any container of references (the plan's output list too)."""
+    def walk(path, v):
+        if isinstance(v, (TRef, FlatRef)):
+            yield path, v
+            if isinstance(v, TRef) and v.tail is not None:
+                yield from walk(path + ".tail", v.tail)
+        elif isinstance(v, (dict, list, tuple)):
+            for k, x in (v.items() if isinstance(v, dict) else enumerate(v)):
+                yield from walk(path + "." + str(k) if path else str(k), x)
+    return walk("", step)
 
 
 def conv_steps(steps):
@@ -133,25 +150,7 @@ class Lowering:
         if not self.h16 or devswitch.get("RD_NO_FUSE_BLOCK"):
             return
         steps = self.plan.steps
-        uses = {}
-
-        def scan(i, key, v):        # every TRef a step holds, also inside nested dicts / lists (fused head_out steps, 'sc' dicts: ADVICE r5)
-            if isinstance(v, (TRef, FlatRef)):
-                uses.setdefault(v.buf, []).append((i, key))
-                if isinstance(v, TRef) and v.tail is not None:
-                    scan(i, key + ".tail", v.tail)
-            elif isinstance(v, dict):
-                for k2, v2 in v.items():
-                    scan(i, key + "." + str(k2), v2)
-            elif isinstance(v, (list, tuple)):
-                for k2, v2 in enumerate(v):
-                    scan(i, key + "." + str(k2), v2)
-        for i, st in enumerate(steps):
-            for key, v in st.items():
-                scan(i, key, v)
-        # a tensor the graph RETURNS has a reader outside the step list: its buffer must survive
-        for o in (self.plan.outputs if isinstance(self.plan.outputs, (list, tuple)) else []):
-            scan(-1, "output", o)
+        uses = self._uses()
 
         def plain64(st, first=False):
             """a folded 3x3 stride-1 conv to 64 channels from 64 channels -- or, as conv1 of the network's first block, from one
@@ -194,11 +193,7 @@ class Lowering:
         if not self.h16:
             return
         steps = self.plan.steps
-        uses = {}
-        for i, st in enumerate(steps):
-            for key, v in st.items():
-                if isinstance(v, TRef):
-                    uses.setdefault(v.buf, []).append((i, key))
+        uses = self._uses()
         drop = set()
         for i, st in enumerate(steps):
             if st["kind"] != "head_out" or st["nout"] > 8:
@@ -206,16 +201,28 @@ class Lowering:
             x = st["x"]
             refs = uses.get(x.buf, [])
             prod = [j for j, key in refs if key == "out"]
-            if len(refs) != 2 or len(prod) != 1 or x.co != 0 or x.C != 128:
+            # exactly one producer and one consumer: the tensor is held by two steps (a step that names it twice is one holder)
+            if len({j for j, _ in refs}) != 2 or len(prod) != 1 or x.co != 0 or x.C != 128:
                 continue
             c = steps[prod[0]]
             if not (c["kind"] == "conv" and tuple(c["k"]) == (3, 3) and c["cout"] == 128 and c["stride_w"] == 1 and
                     c["flags"] == RD_RELU_POST and c.get("res") is None and c["out"] == x and c.get("x2") is None):
                 continue
             c["head"] = dict(name=st["name"], rows=st["rows"], nout=st["nout"], out=st["out"], n_off=st["n_off"], N=st["N"])
-            c["head_out"] = st["out"]        # top level: the executor's buffer liveness pass looks at step values
+            c["head_out"] = st["out"]        # (the same reference as head["out"], for readers of the plan)
             drop.add(i)
         self.plan.steps = [st for i, st in enumerate(steps) if i not in drop]
+
+    def _uses(self):
+        """logical buffer -> [(step index, key path)] of every reference the plan holds (step_refs); a tensor the graph RETURNS has a reader
+        outside the step list, recorded under step index -1, so that its buffer survives the fusions"""
+        uses = {}
+        for i, st in enumerate(self.plan.steps):
+            for path, v in step_refs(st):
+                uses.setdefault(v.buf, []).append((i, path))
+        for path, v in step_refs(self.plan.outputs):
+            uses.setdefault(v.buf, []).append((-1, "output." + path))
+        return uses
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------
     def _count_consumers(self, root):
@@ -342,9 +349,9 @@ class Lowering:
         if sc is not None:
             scx = self.emit_act(sc[0].inputs[0])
             kw["sc"] = dict(name=sc[0].name, bn=sc[1].name, eps=sc[1].attrs["eps"], cin=scx.C, cmap=scx.cmap)
-            kw["sc_x"] = scx                      # top level: the executor's buffer liveness pass looks at step values
+            kw["sc_x"] = scx                      # the shortcut's input tensor
         if x.tail is not None:
-            kw["x2"] = x.tail                     # (top level: buffer liveness)
+            kw["x2"] = x.tail                     # the second tensor of a virtual concat (what selects rd_conv3x3_bn_act_cat)
         self.step("conv", name=conv.name, bn=bn.name, eps=bn.attrs["eps"], x=x, out=out, res=residual,
                   cin=sum(1 for m in x.cmap if m >= 0) if x.tail is not None else x.C,   # (logical channels of a virtual concat)
                   cout=cout, cout_logical=cout_l, k=k, stride_w=sw, flags=flags, cmap=x.cmap, ex=ex, **kw_fold, **kw)
@@ -642,7 +649,6 @@ class Lowering:
         out = FlatRef(self.new_buf(self.B * k * 10 * 4, persistent=True), (k, 10))
         self.step("decode", delta=o_d, pc=o_p, out=out, k=k, box_type=o_d.shape[1], is_bin=int(s.attrs["is_bin"]))
         return out
-
 
     def _batch_riou(self, s):
         """Custom op 'batch_rotated_iou' (operator_py/batch_rotated_iou.py): proposal = a (B,N,10) box tensor of this graph,

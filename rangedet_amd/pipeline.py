@@ -1,8 +1,8 @@
 """End-to-end frame runner: the build's counterpart of the per-frame body of the reference's eval driver
 (tools/test.py:143-161 forward + :184-224 post-process): config -> test symbol -> lowered plan -> Executor, then
-score filter, 10->11 dim, weighted NMS and 12->8 dim on the device.
+score filter, 10->11 dim, weighted NMS and 12->8 dim on the device (one enqueue sequence, RangeDetPipeline._enqueue_post, for the eager and
+the captured path).
 """
-import os
 import numpy as np
 
 from . import devswitch, lib as rdlib
@@ -17,7 +17,6 @@ def input_shapes(H, W, strides=(1, 2, 4), channels=8):
         shapes['pc_vehicle_frame_s%d' % s] = (H * W // s, 3)
         shapes['range_image_mask_s%d' % s] = (H * W // s,)
     return shapes
-
 
 
 def _stream_prio(var):
@@ -233,20 +232,28 @@ class RangeDetPipeline:
                 return outs
         return self._enqueue_eager(inputs)
 
-    def _record(self, inputs):
-        """The batch's whole launch sequence on the CURRENT stream, no events: forward, then per class score filter + NMS + 12 -> 8."""
-        outs = self.exe.forward(inputs)
+    def _enqueue_post(self, outs, stream=None, filtered=lambda: None):
+        """The post-processing of one batch's graph outputs on `stream` (None = the current one): one batched score filter per class -- it is
+        what reads the graph's score / box buffers, so the next batch's forward only has to wait for these short kernels; `filtered()` is
+        called behind them -- then one batched weighted NMS + 12 -> 8 per class for all frames."""
         ptr = lambda t: self.alloc.ptr(t) if hasattr(t, "data_ptr") else t.ctypes.data
-        if not self.wnms:
-            self.bpost.enqueue(ptr(outs[1]), self.k, ptr(outs[2]), ptr(outs[3]), outs[3], stream=None)
-            return outs
+        if not self.wnms:   # outs = [rec_id, score (B,k), bbox_after_nms (B,mk,10), keep_inds (B,mk) int32, ...]: the filter is all there is
+            self.bpost.enqueue(ptr(outs[1]), self.k, ptr(outs[2]), ptr(outs[3]), outs[3], stream=stream)
+            filtered()
+            return
         for ci, c in enumerate(self.class_names):
             sc, bx = outs[1 + 3 * ci], outs[2 + 3 * ci]
             sc_bs = (ptr(sc[1]) - ptr(sc[0])) // 4 if self.batch > 1 else 0
             bx_bs = (ptr(bx[1]) - ptr(bx[0])) // 4 if self.batch > 1 else 0
-            self.bposts[c].enqueue_filter(ptr(sc[0]), sc_bs, ptr(bx[0]), bx_bs, stream=None)
+            self.bposts[c].enqueue_filter(ptr(sc[0]), sc_bs, ptr(bx[0]), bx_bs, stream=stream)
+        filtered()
         for c in self.class_names:
-            self.bposts[c].enqueue_nms(stream=None)
+            self.bposts[c].enqueue_nms(stream=stream)
+
+    def _record(self, inputs):
+        """The batch's whole launch sequence on the CURRENT stream, no events: forward, then per class score filter + NMS + 12 -> 8."""
+        outs = self.exe.forward(inputs)
+        self._enqueue_post(outs)
         return outs
 
     def _enqueue_graph(self, inputs):
@@ -305,24 +312,12 @@ class RangeDetPipeline:
         outs = self.exe.forward(inputs)
         if side:
             A.wait_event(A.record_event(), self._post_stream)
-        # one batched score filter per class (it is what reads the graph's score / box buffers: the next batch's forward only
-        # has to wait for these short kernels), then one batched weighted NMS per class for all frames
-        ptr = lambda t: self.alloc.ptr(t) if hasattr(t, "data_ptr") else t.ctypes.data
-        if not self.wnms:   # outs = [rec_id, score (B,k), bbox_after_nms (B,mk,10), keep_inds (B,mk) int32, ...]
-            sc, bx = outs[1], outs[2]
-            self.bpost.enqueue(ptr(sc), self.k, ptr(bx), ptr(outs[3]), outs[3], stream=self._post_stream)
+
+        def filtered():
             self._filter_done = A.record_event(self._post_stream) if side else None
-            self._post_done = self._filter_done
-            return outs
-        for ci, c in enumerate(self.class_names):
-            sc, bx = outs[1 + 3 * ci], outs[2 + 3 * ci]
-            sc_bs = (ptr(sc[1]) - ptr(sc[0])) // 4 if self.batch > 1 else 0
-            bx_bs = (ptr(bx[1]) - ptr(bx[0])) // 4 if self.batch > 1 else 0
-            self.bposts[c].enqueue_filter(ptr(sc[0]), sc_bs, ptr(bx[0]), bx_bs, stream=self._post_stream)
-        self._filter_done = A.record_event(self._post_stream) if side else None
-        for c in self.class_names:
-            self.bposts[c].enqueue_nms(stream=self._post_stream)
-        self._post_done = A.record_event(self._post_stream) if side else None
+        self._enqueue_post(outs, self._post_stream, filtered)
+        # (the NMS3D branch has nothing behind its filter: one event serves both)
+        self._post_done = (A.record_event(self._post_stream) if side else None) if self.wnms else self._filter_done
         return outs
 
     def collect(self):

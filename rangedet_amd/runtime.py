@@ -1,16 +1,21 @@
 """Executor: binds a lowered Plan (rangedet_amd.lower) to device buffers and parameters and replays it as C-ABI calls
 into librangedet_hip.so on one HIP stream.  PyTorch is used only as the device allocator / stream provider.
 
+Binding happens ONCE, in the constructor: one binder per step kind (Executor._BINDERS) turns a plan step into its library calls, each an
+entry-point name with its complete argument tuple, counted against lib.SIGNATURES there and then.  What stays open until forward() is
+the stream (read per call of forward, always the entry's last argument) and the caller's input tensors (Input slots).  forward()
+resolves those and replays the calls; it knows no step kind.
+
 This is the build's counterpart of the reference's DetModule.bind/set_params/forward/get_outputs
 (utils/detection_module.py:419-510,627-679,783-805) for the test symbol: ``Executor(plan, params).forward(inputs)``
 returns the Group outputs [rec_id, fg_cls_score, decoded_bbox, zeros, gt_bbox_imu, gt_class] (builder.py:77).
 """
-import os
+from collections import namedtuple
 
 import numpy as np
 
 from . import lib as rdlib
-from .lower import FlatRef, TRef
+from .lower import step_refs
 
 
 class TorchAllocator:
@@ -103,6 +108,23 @@ def pad_rows(w, n, axis=0):
     return np.concatenate([w, np.zeros(shp, w.dtype)], axis)
 
 
+def cmap_cols(w, cmap):
+    """weights (cout, logical cin, ...) -> (cout, physical cin, ...): the input buffer carries alignment padding (lower.TRef.cmap, physical ->
+    logical channel or -1), zero weight columns there"""
+    if not cmap:
+        return w
+    wp = np.zeros((w.shape[0], len(cmap)) + w.shape[2:], np.float32)
+    for pc, lc in enumerate(cmap):
+        if lc >= 0:
+            wp[:, pc] = w[:, lc]
+    return wp
+
+
+# An argument the caller supplies per forward(): the float32 device copy of inputs[name]; shape = what its leading dimensions must be
+# (all of them when exact)
+Input = namedtuple("Input", "name shape exact")
+
+
 class Executor:
     def __init__(self, plan, params, lib=None, alloc=None, reuse_buffers=True, keep_sorted_idx=False):
         """keep_sorted_idx: also keep get_sorted_foreground's (B,k) flat indices (parity tests read them with sorted_idx())."""
@@ -113,21 +135,25 @@ class Executor:
         self.dtype = plan.dtype
         self.B = plan.batch
         self._phys = {}
+        self._held = []            # uploaded images and workspaces: the bound calls carry their addresses only
+        self._sorted_idx = []      # per sorted_fg step: (index buffer, k)
         self._assign_buffers(reuse_buffers)
-        self._bound = [self._bind(st, params) for st in plan.steps]
+        self._bound = [self._bind(st, params) for st in plan.steps]   # per step: [(entry, arguments without the stream, input slots)]
 
     # ---- memory ------------------------------------------------------------------------------------------------
     def _assign_buffers(self, reuse):
+        """One allocation per logical buffer; two non-persistent buffers of one size share it when their live ranges -- first to last step
+        holding a reference at any depth (lower.step_refs) -- do not overlap.  A reference to a buffer the plan no longer has (the
+        intermediate tensor inside a fused block) is not a use."""
         plan = self.plan
         last_use, first_def = {}, {}
         for i, st in enumerate(plan.steps):
-            for v in st.values():
-                if isinstance(v, (TRef, FlatRef)):
+            for _, v in step_refs(st):
+                if v.buf in plan.buffers:
                     last_use[v.buf] = i
                     first_def.setdefault(v.buf, i)
-        for kind, v in plan.outputs:
-            if kind in ("flat", "flat_i32"):
-                last_use[v.buf] = len(plan.steps) + 1
+        for _, v in step_refs(plan.outputs):
+            last_use[v.buf] = len(plan.steps) + 1
         free = {}
         release = {}
         for b, i in last_use.items():
@@ -152,246 +178,212 @@ class Executor:
     def p(self, ref):
         return self.alloc.ptr(self._phys[ref.buf])
 
-    # ---- parameter binding -------------------------------------------------------------------------------------------
+    def _up(self, arr):
+        """address of a device copy of `arr` that lives as long as the executor (None stays None)"""
+        if arr is None:
+            return None
+        self._held.append(self.alloc.upload(arr))
+        return self.alloc.ptr(self._held[-1])
+
+    def _ws(self, nbytes):
+        self._held.append(self.alloc.alloc(nbytes))
+        return self._held[-1]
+
+    def _at(self, ref):
+        """(address, channel stride, channel offset) of an activation; (None, 0, 0) for an operand that is not there"""
+        return (self.p(ref), ref.cs, ref.co) if ref is not None else (None, 0, 0)
+
+    # ---- binding: plan step -> library calls -------------------------------------------------------------------------
     def _bind(self, st, P):
-        L, A, dt = self.lib, self.alloc, self.dtype
-        k = st["kind"]
-        b = dict(st)
-        if k == "block":   # a fused BasicBlock (lower._fuse_blocks): both 3x3 weights in one image, the shortcut's as for the unfused conv2
-            ca, cb = st["a"], st["b"]
-            w1, w2 = (np.asarray(P[c["name"] + "_weight"], np.float32) for c in (ca, cb))
-            if ca.get("cmap"):   # (the first block's input buffer carries alignment padding: zero weight columns there)
-                wp = np.zeros((w1.shape[0], len(ca["cmap"])) + w1.shape[2:], np.float32)
-                for pc, lc in enumerate(ca["cmap"]):
-                    if lc >= 0:
-                        wp[:, pc] = w1[:, lc]
-                w1 = wp
-            (s1, t1), (s2, t2) = bn_affine(P, ca["bn"], ca["eps"]), bn_affine(P, cb["bn"], cb["eps"])
-            m16 = bool(st.get("m16")) and w1.shape[1] == 64      # the 16 x 16 x 32 MFMA form (lower._mark_mfma16): its own weight images
-            b["m16"] = m16
-            b["w"] = A.upload(L.pack_block64(w1, s1, w2, s2, dtype=dt, m16=m16))
-            b["shift1"] = A.upload(t1)
-            b["sc_w"] = None
-            if cb.get("sc"):
-                sc = cb["sc"]
-                wsc = np.asarray(P[sc["name"] + "_weight"], np.float32).reshape(64, -1)
-                if sc.get("cmap"):
-                    wq = np.zeros((64, len(sc["cmap"])), np.float32)
-                    for pc, lc in enumerate(sc["cmap"]):
-                        if lc >= 0:
-                            wq[:, pc] = wsc[:, lc]
-                    wsc = wq
-                ss, ts = bn_affine(P, sc["bn"], sc["eps"])
-                b["sc_w"] = A.upload(L.pack_conv1x1_sc_m16(wsc, ss, dtype=dt) if m16 else L.pack_conv1x1_sc(wsc, fold_scale=ss, dtype=dt))
-                t2 = (t2.astype(np.float64) + ts).astype(np.float32)
-            b["shift2"] = A.upload(t2)
-            b["cin"] = w1.shape[1]
-            return b
-        if k == "conv":
-            w = pad_rows(np.asarray(P[st["name"] + "_weight"], np.float32), st["cout"])
-            if st.get("cmap"):   # the input is a concat buffer with alignment padding: zero weight columns there
-                wp = np.zeros((w.shape[0], len(st["cmap"])) + w.shape[2:], np.float32)
-                for pc, lc in enumerate(st["cmap"]):
-                    if lc >= 0:
-                        wp[:, pc] = w[:, lc]
-                w = wp
-            s, t = bn_affine(P, st["bn"], st["eps"], pad_to=st["cout"])
-            if st.get("sc"):      # fused projection shortcut: both BN scales folded into the weights, one shift for the sum
-                sc = st["sc"]
-                wsc = np.asarray(P[sc["name"] + "_weight"], np.float32)
-                wsc = pad_rows(wsc.reshape(wsc.shape[0], -1), st["cout"])
-                if sc.get("cmap"):
-                    wq = np.zeros((w.shape[0], len(sc["cmap"])), np.float32)
-                    for pc, lc in enumerate(sc["cmap"]):
-                        if lc >= 0:
-                            wq[:, pc] = wsc[:, lc]
-                    wsc = wq
-                ss, ts = bn_affine(P, sc["bn"], sc["eps"], pad_to=st["cout"])
-                b["w"] = A.upload(L.pack_conv3x3_ex(w, st["stride_w"], st["x"].cs, fold_scale=s, dtype=dt))
-                b["sc_w"] = A.upload(L.pack_conv1x1_sc(wsc, fold_scale=ss, dtype=dt))
-                b["scale"], b["shift"] = None, A.upload((t.astype(np.float64) + ts).astype(np.float32))
-            elif st.get("x2") is not None:          # conv over the virtual concat [x | x2] (lower._concat)
-                b["w"] = A.upload(L.pack_conv3x3_cat(w, st["x"].C, st["x2"].cs, fold_scale=s, dtype=dt))
-                b["scale"], b["shift"] = None, A.upload(t)
-                b["flags"] = st["flags"] | rdlib.RD_SCALE_FOLDED
-            elif st.get("ex") and st.get("fold") and st.get("m16") and \
-                    L.raw("rd_conv3x3_mfma16_ok")(w.shape[1], st["cout"], 1, st["x"].W, 1 if st.get("head") else 0) == 1:
-                # the same in the 16 x 16 x 32 MFMA form (lower._mark_mfma16)
-                b["w"] = A.upload(L.pack_conv3x3_m16(w, s, dtype=dt))
-                b["scale"], b["shift"] = None, A.upload(t)
-                b["flags"] = st["flags"] | rdlib.RD_SCALE_FOLDED | rdlib.RD_MFMA16
-            elif st.get("ex") and st.get("fold"):   # scale folded into the weights, the shift enters through the accumulators
-                b["w"] = A.upload(L.pack_conv3x3_ex(w, st["stride_w"], st["x"].cs, fold_scale=s, dtype=dt))
-                b["scale"], b["shift"] = None, A.upload(t)
-                b["flags"] = st["flags"] | rdlib.RD_SCALE_FOLDED
-            elif st.get("ex"):
-                b["w"] = A.upload(L.pack_conv3x3_ex(w, st["stride_w"], st["x"].cs, dtype=dt))
-                b["scale"], b["shift"] = A.upload(s), A.upload(t)
-            else:
-                b["w"] = A.upload(L.pack_conv_weight(w, dt))
-                b["scale"], b["shift"] = A.upload(s), A.upload(t)
-        elif k == "deconv":
-            w = pad_rows(np.asarray(P[st["name"] + "_weight"], np.float32), st["cout"], axis=1)      # (cin, cout, kh, kw)
-            s, t = bn_affine(P, st["bn"], st["eps"], pad_to=st["cout"])
-            fs = s if st.get("fold") else None
-            imgs = [L.pack_deconv_weight(w, st["stride_w"], st["pad_w"], ph, dt, fold_scale=fs) for ph in range(st["stride_w"])]
-            # all phases in ONE launch when the library has that form for this layer (16-bit, folded scale, 3 x 2 phases):
-            # the phase images back to back in one buffer
-            b["all_phases"] = bool(st.get("one_launch")) and len({len(i) for i in imgs}) == 1 and \
-                L.raw("rd_deconv2d_all_phases_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt) == 1
-            if st.get("one_launch") and not b["all_phases"] and not L.raw("rd_deconv2d_all_phases_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt):
-                b["one_launch"] = False      # (the library has no such form for this layer: per-phase launches)
-            if b["all_phases"]:
-                b["w_all"], b["w_pb"] = A.upload(np.concatenate(imgs)), len(imgs[0])
-            # phases 2p | 2p+1 as one 128-channel problem where the layer has that form and its tensors are dense (agg1: 128 -> 64, stride 4)
-            r_, o_ = st["res"], st["out"]
-            b["pairs"] = b["all_phases"] and o_.cs == st["cout"] and o_.co == 0 and \
-                (r_ is None or (r_.cs == st["cout"] and r_.co == 0)) and \
-                L.raw("rd_deconv2d_phase_pairs_ok")(st["k"][0], st["k"][1], st["stride_w"], st["pad_w"], st["cout"], dt) == 1
-            if b["pairs"]:
-                pimgs = [L.pack_deconv_phase_pair(imgs[p], imgs[p + 1], st["cin"], dt) for p in range(0, st["stride_w"], 2)]
-                b["w_pairs"], b["w_pairb"], b["shift2"] = A.upload(np.concatenate(pimgs)), len(pimgs[0]), A.upload(np.concatenate([t, t]))
-            b["w"] = [A.upload(i) for i in imgs]
-            b["scale"], b["shift"] = (None if st.get("fold") else A.upload(s)), A.upload(t)
-            if st.get("fold"):
-                b["flags"] = st["flags"] | rdlib.RD_SCALE_FOLDED
-        elif k == "meta":
-            s1, t1 = bn_affine(P, st["bn1"], st["eps1"])
-            s2, t2 = bn_affine(P, st["bn2"], st["eps2"])
-            pk = L.pack_meta(P[st["mlp0"] + "_weight"].reshape(32, 3), P[st["mlp0"] + "_bias"],
-                             P[st["mlp1"] + "_weight"].reshape(64, 32), P[st["mlp1"] + "_bias"], s1, t1,
-                             P[st["agg"] + "_weight"].reshape(64, 576), s2, t2, dt)
-            b["packed"] = A.upload(pk)
-        if k == "conv" and st.get("head"):
+        binder = self._BINDERS.get(st["kind"])
+        if binder is None:
+            raise RuntimeError("unknown plan step %r" % st["kind"])
+        calls = []
+        for name, *args in binder(self, st, P):
+            want = len(rdlib.SIGNATURES[name][1]) - 1          # (the stream, every entry's last argument, is added per forward)
+            if len(args) != want:
+                raise TypeError("step %r (%s): %s bound with %d arguments before the stream, the library takes %d" %
+                                (st.get("name", ""), st["kind"], name, len(args), want))
+            calls.append((name, tuple(args), tuple((j, a) for j, a in enumerate(args) if isinstance(a, Input))))
+        return calls
+
+    def _bind_nchw_in(self, st, P):
+        o, B = st["out"], self.B
+        yield ("rd_nchw_to_nhwc", Input(st["name"], (B, o.C, o.H, o.W), True), self.p(o), B, o.C, o.H, o.W, o.cs, o.co, st["zero_pad"], self.dtype)
+
+    def _bind_block(self, st, P):
+        """a fused BasicBlock (lower._fuse_blocks): both 3x3 weights in one image, the shortcut's as for the unfused conv2"""
+        L, dt = self.lib, self.dtype
+        ca, cb, x, o = st["a"], st["b"], st["x"], st["out"]
+        w1, w2 = (np.asarray(P[c["name"] + "_weight"], np.float32) for c in (ca, cb))
+        w1 = cmap_cols(w1, ca.get("cmap"))      # (the first block's input buffer carries alignment padding)
+        (s1, t1), (s2, t2) = bn_affine(P, ca["bn"], ca["eps"]), bn_affine(P, cb["bn"], cb["eps"])
+        cin = w1.shape[1]
+        m16 = bool(st.get("m16")) and cin == 64      # the 16 x 16 x 32 MFMA form (lower._mark_mfma16): its own weight images
+        sc_w = None
+        if cb.get("sc"):
+            sc = cb["sc"]
+            wsc = cmap_cols(np.asarray(P[sc["name"] + "_weight"], np.float32).reshape(64, -1), sc.get("cmap"))
+            ss, ts = bn_affine(P, sc["bn"], sc["eps"])
+            sc_w = L.pack_conv1x1_sc_m16(wsc, ss, dtype=dt) if m16 else L.pack_conv1x1_sc(wsc, fold_scale=ss, dtype=dt)
+            t2 = (t2.astype(np.float64) + ts).astype(np.float32)
+        tail = (self._up(L.pack_block64(w1, s1, w2, s2, dtype=dt, m16=m16)), self._up(t1), self._up(t2), self._up(sc_w),
+                *self._at(o), self.B, x.H, x.W, dt)
+        if m16:
+            yield ("rd_block64_m16_bn_act", *self._at(x), *tail)
+        else:
+            yield ("rd_block64_bn_act", *self._at(x), cin, *tail)
+
+    def _conv_form(self, st, cin):
+        """How a conv step is launched, decided here and nowhere else.  Returns (form, m16): form = "plain" (the tap kernel), "ex" (the
+        persistent 3x3 kernel), "ex_fold" (BatchNorm scale folded into the weights), "ex_sc" (fused projection shortcut), "cat" (two-tensor
+        input) or "head" (fused output conv); m16 = the 16 x 16 x 32 MFMA form of "ex_fold" / "head", when the lowering asked for it
+        (lower._mark_mfma16) and the library has it for this shape.  cin: physical input channels."""
+        head, sc, cat = bool(st.get("head")), bool(st.get("sc")), st.get("x2") is not None
+        fold = bool(st.get("ex") and st.get("fold"))
+        if head + sc + cat > 1 or ((head or sc) and not st.get("ex")):
+            raise NotImplementedError("conv step %r: no launch form for head=%s sc=%s x2=%s ex=%s" % (st["name"], head, sc, cat, st.get("ex")))
+        if sc or cat:
+            return ("ex_sc" if sc else "cat"), False
+        m16 = fold and bool(st.get("m16")) and \
+            self.lib.raw("rd_conv3x3_mfma16_ok")(cin, st["cout"], 1, st["x"].W, 1 if head else 0) == 1
+        return ("head" if head else "ex_fold" if fold else "ex" if st.get("ex") else "plain"), m16
+
+    def _bind_conv(self, st, P):
+        L, dt, B = self.lib, self.dtype, self.B
+        x, o, r, cout, sw = st["x"], st.get("out"), st.get("res"), st["cout"], st["stride_w"]
+        w = cmap_cols(pad_rows(np.asarray(P[st["name"] + "_weight"], np.float32), cout), st.get("cmap"))
+        s, t = bn_affine(P, st["bn"], st["eps"], pad_to=cout)
+        form, m16 = self._conv_form(st, w.shape[1])
+        folded = form in ("cat", "ex_fold") or (form == "head" and st.get("fold"))
+        flags = st["flags"] | (rdlib.RD_SCALE_FOLDED if folded else 0) | (rdlib.RD_MFMA16 if m16 else 0)
+        scale = None if folded or form == "ex_sc" else self._up(s)
+        if form == "plain":
+            yield ("rd_conv2d_bn_act", *self._at(x), self._up(L.pack_conv_weight(w, dt)), scale, self._up(t), *self._at(r), *self._at(o),
+                   B, x.H, x.W, st["cin"], cout, st["k"][0], st["k"][1], sw, flags, dt)
+            return
+        if form == "cat":       # conv over the virtual concat [x | x2] (lower._concat): neither a shared buffer nor a copy exists
+            x2 = st["x2"]
+            yield ("rd_conv3x3_bn_act_cat", *self._at(x), x.C, *self._at(x2), x2.cs, self._up(L.pack_conv3x3_cat(w, x.C, x2.cs, fold_scale=s, dtype=dt)),
+                   self._up(t), *self._at(o), B, x.H, x.W, cout, flags, dt)
+            return
+        # the persistent 3x3 kernel: scale folded into the weights (the shift then enters through the accumulators) or passed beside them
+        wimg = self._up(L.pack_conv3x3_m16(w, s, dtype=dt) if m16 else
+                        L.pack_conv3x3_ex(w, sw, x.cs, fold_scale=None if scale is not None else s, dtype=dt))
+        if form == "head":      # fused 1x1 output conv (lower._fuse_head_out): the tower output is never written
             h = st["head"]
             r0, r1 = h["rows"]
-            hw = np.asarray(P[h["name"] + "_weight"], np.float32).reshape(-1, st["cout"])[r0:r1]
-            b["head_w"] = A.upload(L.pack_head_weight(hw, dtype=dt, m16=bool(b.get("flags", 0) & rdlib.RD_MFMA16)))
-            b["head_bias"] = A.upload(np.asarray(P[h["name"] + "_bias"], np.float32)[r0:r1])
-        elif k == "head_out":
-            r0, r1 = st["rows"]
-            w = np.asarray(P[st["name"] + "_weight"], np.float32).reshape(-1, st["x"].C)[r0:r1]
-            b["w"] = A.upload(w)
-            b["bias"] = A.upload(np.asarray(P[st["name"] + "_bias"], np.float32)[r0:r1])
-        elif k == "nms3d":
-            nb = L.raw("rd_nms3d_workspace_bytes")(st["N"], self.B)
-            b["ws"] = A.alloc(nb)
-            b["ws_bytes"] = nb
-        elif k == "sorted_fg":
-            nb = L.raw("rd_sorted_foreground_workspace_bytes")(st["N"], st["k"]) * self.B
-            b["ws"] = A.alloc(nb)
-            b["ws_bytes"] = nb
-            b["idx"] = A.alloc(self.B * st["k"] * 4) if self.keep_sorted_idx else None
-        return b
+            hw = np.asarray(P[h["name"] + "_weight"], np.float32).reshape(-1, cout)[r0:r1]
+            yield ("rd_conv2d_bn_act_head_out", *self._at(x), wimg, scale, self._up(t), B, x.H, x.W, st["cin"], flags,
+                   self._up(L.pack_head_weight(hw, dtype=dt, m16=m16)), self._up(np.asarray(P[h["name"] + "_bias"], np.float32)[r0:r1]),
+                   self.p(h["out"]), h["N"] * h["nout"], h["n_off"], h["nout"], dt)
+            return
+        sc_x, sc_cin, sc_w = None, 0, None
+        if form == "ex_sc":     # fused projection shortcut: both BN scales folded into the weights, one shift for the sum
+            sc, sc_x = st["sc"], st["sc_x"]
+            wsc = np.asarray(P[sc["name"] + "_weight"], np.float32)
+            wsc = cmap_cols(pad_rows(wsc.reshape(wsc.shape[0], -1), cout), sc.get("cmap"))
+            ss, ts = bn_affine(P, sc["bn"], sc["eps"], pad_to=cout)
+            sc_cin, sc_w = len(sc["cmap"]) if sc.get("cmap") else sc["cin"], self._up(L.pack_conv1x1_sc(wsc, fold_scale=ss, dtype=dt))
+            t = (t.astype(np.float64) + ts).astype(np.float32)
+        yield ("rd_conv3x3_bn_act_ex", *self._at(x), wimg, scale, self._up(t), *self._at(r), *self._at(sc_x), sc_cin, sc_w, *self._at(o),
+               B, x.H, x.W, len(st["cmap"]) if st.get("cmap") else st["cin"], cout, sw, flags, dt)
+
+    def _bind_deconv(self, st, P):
+        """per-phase launches, or -- where the lowering asked (one_launch) and the library has the form for this layer -- all phases in ONE
+        launch (the phase images back to back), or phases 2p | 2p+1 as one 128-channel problem where its tensors are dense besides (agg1:
+        128 -> 64, stride 4).  Only the images of the form that is launched are uploaded."""
+        L, dt = self.lib, self.dtype
+        x, o, r, cout, sw, pw, (kh, kw) = st["x"], st["out"], st["res"], st["cout"], st["stride_w"], st["pad_w"], st["k"]
+        w = pad_rows(np.asarray(P[st["name"] + "_weight"], np.float32), cout, axis=1)      # (cin, cout, kh, kw)
+        s, t = bn_affine(P, st["bn"], st["eps"], pad_to=cout)
+        fold = bool(st.get("fold"))
+        imgs = [L.pack_deconv_weight(w, sw, pw, ph, dt, fold_scale=s if fold else None) for ph in range(sw)]
+        flags = st["flags"] | (rdlib.RD_SCALE_FOLDED if fold else 0)
+        geom = (*self._at(r), *self._at(o), self.B, x.H, x.W, st["cin"], cout, kh, kw, sw, pw)
+        dense = all(v.cs == cout and v.co == 0 for v in (o, r) if v is not None)
+        all_phases = bool(st.get("one_launch")) and len({len(i) for i in imgs}) == 1 and \
+            L.raw("rd_deconv2d_all_phases_ok")(kh, kw, sw, pw, cout, dt) == 1
+        if all_phases and dense and L.raw("rd_deconv2d_phase_pairs_ok")(kh, kw, sw, pw, cout, dt) == 1:
+            pimgs = [L.pack_deconv_phase_pair(imgs[p], imgs[p + 1], st["cin"], dt) for p in range(0, sw, 2)]
+            yield ("rd_deconv2d_bn_act_pairs", *self._at(x), self._up(np.concatenate(pimgs)), len(pimgs[0]), self._up(np.concatenate([t, t])),
+                   *geom, flags, dt)
+        elif all_phases:
+            yield ("rd_deconv2d_bn_act_all", *self._at(x), self._up(np.concatenate(imgs)), len(imgs[0]), self._up(t), *geom, flags, dt)
+        else:
+            scale, shift = (None if fold else self._up(s)), self._up(t)
+            for ph in range(sw):
+                yield ("rd_deconv2d_bn_act", *self._at(x), self._up(imgs[ph]), scale, shift, *geom, ph, flags, dt)
+
+    def _bind_meta(self, st, P):
+        x, o, B = st["x"], st["out"], self.B
+        s1, t1 = bn_affine(P, st["bn1"], st["eps1"])
+        s2, t2 = bn_affine(P, st["bn2"], st["eps2"])
+        pk = self.lib.pack_meta(P[st["mlp0"] + "_weight"].reshape(32, 3), P[st["mlp0"] + "_bias"],
+                                P[st["mlp1"] + "_weight"].reshape(64, 32), P[st["mlp1"] + "_bias"], s1, t1,
+                                P[st["agg"] + "_weight"].reshape(64, 576), s2, t2, self.dtype)
+        yield ("rd_meta_kernel_fwd", *self._at(x), Input(st["coord"], (B, 3, x.H, x.W), True), self._up(pk), *self._at(o), B, x.H, x.W, self.dtype)
+
+    def _bind_head_out(self, st, P):
+        x = st["x"]
+        r0, r1 = st["rows"]
+        w = np.asarray(P[st["name"] + "_weight"], np.float32).reshape(-1, x.C)[r0:r1]
+        yield ("rd_head_out", *self._at(x), self._up(w), self._up(np.asarray(P[st["name"] + "_bias"], np.float32)[r0:r1]), self.p(st["out"]),
+               st["N"] * st["nout"], st["n_off"], self.B, x.H, x.W, x.C, st["nout"], self.dtype)
+
+    def _bind_concat_in(self, st, P):
+        row = st["N"] * st["last"] * 4                      # bytes of one frame's concatenated row
+        off = 0
+        for name, n in st["names"]:
+            yield ("rd_copy_rows", Input(name, (self.B, n), False), n * st["last"] * 4, self.p(st["out"]), row, off * st["last"] * 4,
+                   n * st["last"] * 4, self.B)
+            off += n
+
+    def _bind_sorted_fg(self, st, P):
+        A, B = self.alloc, self.B
+        nb = self.lib.raw("rd_sorted_foreground_workspace_bytes")(st["N"], st["k"]) * B
+        idx = self._ws(B * st["k"] * 4) if self.keep_sorted_idx else None
+        self._sorted_idx.append((idx, st["k"]))
+        yield ("rd_sorted_foreground", self.p(st["score"]), self.p(st["delta"]), self.p(st["pc"]), self.p(st["mask"]), B, st["N"], st["k"],
+               st["D"], st["apply_sigmoid"], self.p(st["out_score"]), self.p(st["out_delta"]), self.p(st["out_pc"]),
+               A.ptr(idx) if idx is not None else None, A.ptr(self._ws(nb)), nb)
+
+    def _bind_decode(self, st, P):
+        yield ("rd_decode3d_bbox", self.p(st["delta"]), self.p(st["pc"]), self.p(st["out"]), self.B, st["k"], st["box_type"], st["is_bin"])
+
+    def _bind_batch_riou(self, st, P):
+        three_d = st.get("iou_type", "bev") == "3d"
+        yield ("rd_batch_rotated_iou_3d" if three_d else "rd_batch_rotated_iou", self.p(st["boxes"]), 10,
+               Input(st["gt"], (self.B, st["n_gt"], 7 if three_d else 8), True), self.p(st["out"]), None, self.B, st["N"], st["n_gt"])
+
+    def _bind_nms3d(self, st, P):
+        nb = self.lib.raw("rd_nms3d_workspace_bytes")(st["N"], self.B)
+        yield ("rd_nms3d", self.p(st["boxes"]), self.B, st["N"], st["thr"], st["max_keep"], st["normal_iou"], self.p(st["keep"]),
+               self.p(st["out"]), self.alloc.ptr(self._ws(nb)), nb)
+
+    _BINDERS = {"nchw_in": _bind_nchw_in, "block": _bind_block, "conv": _bind_conv, "deconv": _bind_deconv, "meta": _bind_meta,
+                "head_out": _bind_head_out, "concat_in": _bind_concat_in, "sorted_fg": _bind_sorted_fg, "decode": _bind_decode,
+                "batch_riou": _bind_batch_riou, "nms3d": _bind_nms3d}
 
     # ---- execution ------------------------------------------------------------------------------------------------------
     def forward(self, inputs, only=None, dev=None):
         """inputs: name -> float32 array/tensor WITH batch dim (the reference's data_name list, config:400-404).
-        `only` (profiling aid): run just that plan step index."""
-        L, A, dt, B = self.lib, self.alloc, self.dtype, self.B
-        st_ = A.stream
+        `only` (profiling aid): run just that plan step index.  `dev`: a dict that keeps the inputs' device copies between calls."""
+        A, B = self.alloc, self.B
+        call, stream = self.lib.call, A.stream
         dev = {} if dev is None else dev
-
-        def din(name):
-            if name not in dev:
-                dev[name] = A.as_device_f32(inputs[name])
-            return dev[name]
-
-        steps = self._bound if only is None else [self._bound[only]]
-        for b in steps:
-            k = b["kind"]
-            if k == "nchw_in":
-                o = b["out"]
-                src = din(b["name"])
-                assert tuple(src.shape) == (B, o.C, o.H, o.W), (b["name"], tuple(src.shape), (B, o.C, o.H, o.W))
-                L.call("rd_nchw_to_nhwc", A.ptr(src), self.p(o), B, o.C, o.H, o.W, o.cs, o.co, b["zero_pad"], dt, st_)
-            elif k == "block":
-                x, o = b["x"], b["out"]
-                if b.get("m16"):
-                    L.call("rd_block64_m16_bn_act", self.p(x), x.cs, x.co, A.ptr(b["w"]), A.ptr(b["shift1"]), A.ptr(b["shift2"]),
-                           A.ptr(b["sc_w"]) if b["sc_w"] is not None else None, self.p(o), o.cs, o.co, B, x.H, x.W, dt, st_)
-                else:
-                    L.call("rd_block64_bn_act", self.p(x), x.cs, x.co, b["cin"], A.ptr(b["w"]), A.ptr(b["shift1"]), A.ptr(b["shift2"]),
-                           A.ptr(b["sc_w"]) if b["sc_w"] is not None else None, self.p(o), o.cs, o.co, B, x.H, x.W, dt, st_)
-            elif k == "conv" and b.get("head"):
-                x, h = b["x"], b["head"]
-                L.call("rd_conv2d_bn_act_head_out", self.p(x), x.cs, x.co, A.ptr(b["w"]),
-                       A.ptr(b["scale"]) if b["scale"] is not None else None, A.ptr(b["shift"]), B,
-                       x.H, x.W, b["cin"], b["flags"], A.ptr(b["head_w"]), A.ptr(b["head_bias"]), self.p(h["out"]),
-                       h["N"] * h["nout"], h["n_off"], h["nout"], dt, st_)
-            elif k == "conv" and b.get("x2") is not None:
-                # conv over the virtual concat [x | x2] (lower._concat): neither a shared buffer nor a copy exists
-                x, x2, o = b["x"], b["x2"], b["out"]
-                L.call("rd_conv3x3_bn_act_cat", self.p(x), x.cs, x.co, x.C, self.p(x2), x2.cs, x2.co, x2.cs, A.ptr(b["w"]), A.ptr(b["shift"]),
-                       self.p(o), o.cs, o.co, B, x.H, x.W, b["cout"], b["flags"], dt, st_)
-            elif k == "conv" and b.get("ex"):
-                x, o, r, sx = b["x"], b["out"], b["res"], b.get("sc_x")
-                cin = len(b["cmap"]) if b.get("cmap") else b["cin"]
-                L.call("rd_conv3x3_bn_act_ex", self.p(x), x.cs, x.co, A.ptr(b["w"]), A.ptr(b["scale"]) if b["scale"] is not None else None,
-                       A.ptr(b["shift"]), self.p(r) if r else None, r.cs if r else 0, r.co if r else 0,
-                       self.p(sx) if sx else None, sx.cs if sx else 0, sx.co if sx else 0,
-                       (len(b["sc"]["cmap"]) if b["sc"].get("cmap") else b["sc"]["cin"]) if sx else 0,
-                       A.ptr(b["sc_w"]) if sx else None, self.p(o), o.cs, o.co, B, x.H, x.W, cin, b["cout"], b["stride_w"],
-                       b["flags"], dt, st_)
-            elif k == "conv":
-                x, o, r = b["x"], b["out"], b["res"]
-                L.call("rd_conv2d_bn_act", self.p(x), x.cs, x.co, A.ptr(b["w"]), A.ptr(b["scale"]), A.ptr(b["shift"]),
-                       self.p(r) if r else None, r.cs if r else 0, r.co if r else 0, self.p(o), o.cs, o.co, B, x.H, x.W,
-                       b["cin"], b["cout"], b["k"][0], b["k"][1], b["stride_w"], b["flags"], dt, st_)
-            elif k == "deconv":
-                x, o, r = b["x"], b["out"], b["res"]
-                if b.get("pairs"):
-                    L.call("rd_deconv2d_bn_act_pairs", self.p(x), x.cs, x.co, A.ptr(b["w_pairs"]), b["w_pairb"], A.ptr(b["shift2"]), self.p(r), r.cs,
-                           r.co, self.p(o), o.cs, o.co, B, x.H, x.W, b["cin"], b["cout"], b["k"][0], b["k"][1], b["stride_w"], b["pad_w"],
-                           b["flags"], dt, st_)
-                    continue
-                if b.get("all_phases"):
-                    L.call("rd_deconv2d_bn_act_all", self.p(x), x.cs, x.co, A.ptr(b["w_all"]), b["w_pb"], A.ptr(b["shift"]), self.p(r), r.cs,
-                           r.co, self.p(o), o.cs, o.co, B, x.H, x.W, b["cin"], b["cout"], b["k"][0], b["k"][1], b["stride_w"], b["pad_w"],
-                           b["flags"], dt, st_)
-                    continue
-                for ph in range(b["stride_w"]):
-                    L.call("rd_deconv2d_bn_act", self.p(x), x.cs, x.co, A.ptr(b["w"][ph]),
-                           A.ptr(b["scale"]) if b["scale"] is not None else None, A.ptr(b["shift"]), self.p(r), r.cs, r.co, self.p(o), o.cs, o.co, B, x.H, x.W, b["cin"],
-                           b["cout"], b["k"][0], b["k"][1], b["stride_w"], b["pad_w"], ph, b["flags"], dt, st_)
-            elif k == "meta":
-                x, o = b["x"], b["out"]
-                c = din(b["coord"])
-                assert tuple(c.shape) == (B, 3, x.H, x.W)
-                L.call("rd_meta_kernel_fwd", self.p(x), x.cs, x.co, A.ptr(c), A.ptr(b["packed"]), self.p(o), o.cs, o.co,
-                       B, x.H, x.W, dt, st_)
-            elif k == "head_out":
-                x, o = b["x"], b["out"]
-                L.call("rd_head_out", self.p(x), x.cs, x.co, A.ptr(b["w"]), A.ptr(b["bias"]), self.p(o),
-                       b["N"] * b["nout"], b["n_off"], B, x.H, x.W, x.C, b["nout"], dt, st_)
-            elif k == "concat_in":
-                o = b["out"]
-                row = b["N"] * b["last"] * 4                      # bytes of one frame's concatenated row
-                off = 0
-                for name, n in b["names"]:
-                    src = din(name)
-                    assert tuple(src.shape)[:2] == (B, n), (name, tuple(src.shape))
-                    L.call("rd_copy_rows", A.ptr(src), n * b["last"] * 4, self.p(o), row, off * b["last"] * 4,
-                           n * b["last"] * 4, B, st_)
-                    off += n
-            elif k == "sorted_fg":
-                L.call("rd_sorted_foreground", self.p(b["score"]), self.p(b["delta"]), self.p(b["pc"]), self.p(b["mask"]),
-                       B, b["N"], b["k"], b["D"], b["apply_sigmoid"], self.p(b["out_score"]), self.p(b["out_delta"]),
-                       self.p(b["out_pc"]), A.ptr(b["idx"]) if b["idx"] is not None else None, A.ptr(b["ws"]), b["ws_bytes"], st_)
-            elif k == "decode":
-                L.call("rd_decode3d_bbox", self.p(b["delta"]), self.p(b["pc"]), self.p(b["out"]), B, b["k"],
-                       b["box_type"], b["is_bin"], st_)
-            elif k == "batch_riou":
-                g = din(b["gt"])
-                three_d = b.get("iou_type", "bev") == "3d"
-                assert tuple(g.shape) == (B, b["n_gt"], 7 if three_d else 8), (b["gt"], tuple(g.shape))
-                L.call("rd_batch_rotated_iou_3d" if three_d else "rd_batch_rotated_iou", self.p(b["boxes"]), 10, A.ptr(g), self.p(b["out"]),
-                       None, B, b["N"], b["n_gt"], st_)
-            elif k == "nms3d":
-                L.call("rd_nms3d", self.p(b["boxes"]), B, b["N"], b["thr"], b["max_keep"], b["normal_iou"], self.p(b["keep"]),
-                       self.p(b["out"]), A.ptr(b["ws"]), b["ws_bytes"], st_)
-            else:
-                raise RuntimeError("unknown plan step %r" % k)
+        for calls in (self._bound if only is None else [self._bound[only]]):
+            for name, args, slots in calls:
+                if slots:
+                    args = list(args)
+                    for j, slot in slots:
+                        if slot.name not in dev:
+                            dev[slot.name] = A.as_device_f32(inputs[slot.name])
+                        src = dev[slot.name]
+                        shape = tuple(src.shape)
+                        assert (shape if slot.exact else shape[:len(slot.shape)]) == slot.shape, (slot.name, shape, slot.shape)
+                        args[j] = A.ptr(src)
+                call(name, *args, stream)
         if only is not None:
             return None
         outs = []
@@ -413,9 +405,9 @@ class Executor:
 
     def sorted_idx(self, which=0):
         """(B,k) int32 flat indices chosen by the which-th get_sorted_foreground step (needs keep_sorted_idx=True)."""
-        b = [x for x in self._bound if x["kind"] == "sorted_fg"][which]
+        idx, k = self._sorted_idx[which]
         self.alloc.sync()
-        return np.array(self.alloc.to_numpy(self.alloc.view_i32(b["idx"], (self.B, b["k"]))))
+        return np.array(self.alloc.to_numpy(self.alloc.view_i32(idx, (self.B, k))))
 
     def debug_tensor(self, ref):
         """NCHW float32 numpy copy of an activation (tests only)."""

@@ -111,6 +111,21 @@ class NumpyAllocator:
         pass
 
 
+class RecordingLib:
+    """Stand-in for rangedet_amd.lib.Lib that launches nothing: call() records (entry, arguments) in `calls`; the host-side packers and
+    the library's queries (raw) are those of the library it wraps.  An Executor bound with it and a NumpyAllocator needs no device."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def call(self, name, *args):
+        self.calls.append((name, args))
+        return 0
+
+
 def small_shapes(H, W):
     shapes = {'input_data': (8, H, W), 'coord_s1': (3, H, W)}
     for s in (1, 2, 4):

@@ -19,9 +19,9 @@ import sys, re, collections
 z, nz = collections.Counter(), collections.Counter()
 for l in sys.stdin:
     m = re.match(r'step +\\d+ (\\S+).*cout (\\S+) W.*: (\\d+) of', l)
-    k = '%-10s cout %s' % (m.group(1), m.group(2))
+    k = '%-26s cout %s' % (m.group(1), m.group(2))
     (z if m.group(3) == '0' else nz)[k] += 1
-for k in sorted(set(z) | set(nz)): print('    %-22s differing in %2d step(s), clean in %2d' % (k, nz[k], z[k]))
+for k in sorted(set(z) | set(nz)): print('    %-38s differing in %2d step(s), clean in %2d' % (k, nz[k], z[k]))
 "
   fi
 } > $O/study.txt 2>&1

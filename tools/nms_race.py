@@ -4,7 +4,7 @@ or two.  This tool found the cause: the chain (rd_wnms_4c_batche
 times on a side stream while another pipeline's forward runs on a second stream, and compared with the result of the same call on an
 idle GPU; on a difference the intermediate arrays in the workspace (prep records, processing order, thr / vote matrices, alive list)
 are compared stage by stage.
-    [TIE=stable] [LOAD=forward|none|matmul|kind:<plan step kind>|sweep] [LREP=3] python tools/nms_race.py [reps]
+    [TIE=stable] [LOAD=forward|none|matmul|kind:<library entry, e.g. rd_conv3x3_bn_act_ex>|sweep] [LREP=3] python tools/nms_race.py [reps]
   LOAD=sweep   every plan step on its own as the concurrent load (which launches matter: the cout-64 ones, two workgroups per CU)
   RANGEDET_HIP_LIB=<a build with the SLP vectoriser>  reproduces the fault; the shipped build gives 0 of N
 """
@@ -118,17 +118,15 @@ MB = torch.empty_like(MA)
 DEV = {}
 
 
-def subkind(b):
-    k = b["kind"]
-    if k == "conv":
-        return "conv_head" if b.get("head") else "conv_cat" if b.get("x2") is not None else "conv_ex" if b.get("ex") else "conv_plain"
-    return k
+def entries(calls):
+    """the library entry point(s) a bound plan step calls (Executor._bound: per step a list of (entry, arguments, input slots))"""
+    return "+".join(sorted({name for name, _, _ in calls}))
 
 
-LIDX = [i for i, b in enumerate(pb.exe._bound) if LOAD == "kind:" + subkind(b)]
+LIDX = [i for i, calls in enumerate(pb.exe._bound) if LOAD == "kind:" + entries(calls)]
 LREP = int(os.environ.get("LREP", "3"))
 if LOAD.startswith("kind:"):
-    print("steps of", LOAD, ":", len(LIDX), "of kinds", sorted(set(subkind(b) for b in pb.exe._bound)))
+    print("steps of", LOAD, ":", len(LIDX), "of entries", sorted(set(entries(c) for c in pb.exe._bound)))
     pb.exe.forward(fr2)
     torch.cuda.synchronize()
 # a second victim: a plain element-wise kernel of the library (no LDS, no atomics)
@@ -142,7 +140,7 @@ vbad = 0
 if LOAD == "sweep":       # every plan step on its own as the concurrent load
     pb.exe.forward(fr2)
     torch.cuda.synchronize()
-    for i, b in enumerate(pb.exe._bound):
+    for i, (b, calls) in enumerate(zip(pb.plan.steps, pb.exe._bound)):
         nb = 0
         for r in range(reps):
             with torch.cuda.stream(s1):
@@ -153,7 +151,7 @@ if LOAD == "sweep":       # every plan step on its own as the concurrent load
             s = snap()
             nb += not (all(np.array_equal(a, c) for a, c in zip(s[1], base[1])) and all(np.array_equal(a, c) for a, c in zip(s[2], base[2])))
         x = b.get("x")
-        print("step %2d %-10s %-28s cin %s cout %s W %s: %d of %d differ" % (i, subkind(b), b.get("name", "")[:28], b.get("cin"), b.get("cout"), getattr(x, "W", None), nb, reps), flush=True)
+        print("step %2d %-26s %-28s cin %s cout %s W %s: %d of %d differ" % (i, entries(calls), b.get("name", "")[:28], b.get("cin"), b.get("cout"), getattr(x, "W", None), nb, reps), flush=True)
     sys.exit(0)
 bad = 0
 for r in range(reps):
