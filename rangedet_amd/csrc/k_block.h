@@ -62,7 +62,7 @@ constexpr bool bk_fetches(bool first, int g) { return bk_unit(first, g) == 3 || 
 constexpr int bk_pieces_u(int s) { return s <= 1 ? 2 : s <= 4 ? 1 : 0; }
 constexpr int bk_first_u(int s) { int n = 0; for (int t = 0; t < s; ++t) n += bk_pieces_u(t); return n; }
 constexpr int bk_pieces(bool first, int g) { return bk_fetches(first, g) ? bk_pieces_u(bk_ord(first, g)) : 0; }   // g = step of the tile (cyclic)
-// DMA instructions a wave issued after "its part of slab g + 2" as seen at the wait of step g (k_conv3.h c3_younger; IPW = 1)
+// DMA instructions a wave issued after "its part of slab g + 2" as seen at the wait of step g (k_conv3.h c3_step, C3Step::wait; IPW = 1)
 constexpr int bk_younger(bool first, int g) {
   const int G = bk_nsteps(first);
   int n = BK_R - 3;

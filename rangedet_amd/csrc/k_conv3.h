@@ -11,14 +11,17 @@
 //           the halo of unit u+1 (possibly the next tile) is fetched by LDS-DMA while unit u is computed;
 //   step  = (unit, tap): one weight slab Cout x 32 ch = NCT*2 KB, kept in MFMA-fragment order (a linear copy of the
 //           packed global image) in an R-deep LDS ring filled by LDS-DMA R steps ahead;
+//   body  = the cyclic sequence of units a tile repeats (C3Body: one unit of 9 or 6 steps, or up to four of different lengths);
+//           everything a step needs at compile time is one descriptor, C3Step = c3_step(body, global step), consumed by the one
+//           step macro of each MFMA form (C3_STEP, C3_STEP16);
 //   one workgroup barrier per step (= 2 k-steps x 4*NCT MFMAs per wave), placed between the two k-steps so that the
 //   LDS reads it retires were issued a whole MFMA block earlier.  Fragments for the next k-step are always read
 //   before the MFMA block of the current one (explicit register double buffer), because with one wave per SIMD
 //   nothing else hides LDS latency.
 //
 // All DMA traffic of a wave retires in order, so "my part of slab g+1 has landed" is a counted s_waitcnt vmcnt(N) with
-// N = DMA instructions issued after it -- a compile-time constant per tap because every step issues exactly IPW slab
-// instructions and every unit 10 (8 x 32: 6) halo instructions (dummy re-fetches keep that true at the end of the list).
+// N = DMA instructions issued after it -- a compile-time constant per step of the body (C3Step::wait) because every step issues exactly
+// IPW slab instructions and every unit 10 (8 x 32: 6) halo instructions (dummy re-fetches keep that true at the end of the list).
 // LDS bytes per MFMA: (4 + NCT) KB / (4*NCT) = 0.5 KB (cout 128), 0.75 KB (cout 64) -- a quarter of ds_read_b128 peak.
 #pragma once
 #include "k_conv.h"
@@ -197,47 +200,24 @@ inline void pack_sc_frag(const float* w, const float* scale, int cin, int cout, 
       }
 }
 
-// Tap sets.  TS = 0: all nine taps (convs).  A transposed-conv phase only has taps in two of the three columns:
-// TS = 1 -> dw in {-1, 0}, TS = 2 -> dw in {0, +1}; its unit is 6 steps instead of 9 (no MFMAs on zero weights).
-constexpr int c3_nsteps(int TS) { return TS == 0 ? 9 : 6; }
-// TS = 3: a two-column tap set whose side (1 or 2) is a run-time property of the tile (Conv3Args::ts_mask): numbered like TS 1, the
-// column index T % 3 in {0, 1} then selects one of the tile's two column offsets instead of a fixed one
-constexpr int c3_tap(int TS, int s) {            // tap index T = 3*(dh+1) + (dw+1) of step ordinal s
-  return TS == 0 ? s : 3 * (s / 2) + (s % 2) + (TS == 2 ? 1 : 0);
-}
-// Halo pieces per step ordinal, all issued at least two steps before the wait that must cover them (ordinal NS-2).
-//   8 x 62 (10 per wave and unit): 2 each at ordinals 0..4 of a 9-step unit; 4, 4, 2 at ordinals 0..2 of a 6-step unit;
-//   8 x 32 (6 per wave and unit):  2, 1, 1, 1, 1 at ordinals 0..4 of a 9-step unit; 2 each at ordinals 0..2 of a 6-step unit.
-constexpr int c3_halo_last(int NS) { return NS == 9 ? 4 : 2; }   // ordinal of the last piece (either tile)
-constexpr int c3_halo_pieces(int s, int NS, C3Tile tile) {
-  return tile == C3_8x32 ? (NS == 9 ? (s == 0 ? 2 : s <= 4 ? 1 : 0) : (s <= 2 ? 2 : 0))
-                         : (NS == 9 ? (s <= 4 ? 2 : 0) : (s <= 1 ? 4 : (s == 2 ? 2 : 0)));
-}
-constexpr int c3_halo_first(int s, int NS, C3Tile tile) { int n = 0; for (int t = 0; t < s; ++t) n += c3_halo_pieces(t, NS, tile); return n; }
-// DMA instructions a wave issues after "its part of slab g+2", as seen at the wait of step g (ordinal s of its unit):
-// the halo pieces of step g+2-R plus everything of steps g+3-R .. g-1.  Every step issues IPW slab instructions plus its
-// halo pieces.  At ordinal NS-2 the wait must also cover the last halo piece: the following step reads the next halo.
-constexpr int c3_younger(int R, int IPW, int s, int NS, C3Tile tile) {
-  int n = (R - 3) * IPW;
-  for (int d = 1; d <= R - 2; ++d) n += c3_halo_pieces((((s - d) % NS) + NS) % NS, NS, tile);
-  const int cap = (NS - 3 - c3_halo_last(NS)) * IPW;
-  if (s == NS - 2 && n > cap) n = cap;
-  return n;
-}
-// ---- tile bodies with units of DIFFERENT step counts (round 4, 8 x 32 tiles only) --------------------------------------------------
-// A tile is normally nchunk units of the same kind (9 or 6 steps).  Three layer classes carry structural zeros in that form:
+// ---- tile bodies, units and steps ---------------------------------------------------------------------------------------------------
+// A tile is a.nchunk UNITS (one 32-channel chunk of the input times its taps); a STEP of a unit is one weight slab = two 16-channel
+// k-steps.  A BODY is a fixed cyclic sequence of up to four units of possibly different kinds; the tile runs it a.nchunk / nu times.
+// Unit kinds:
+//   UK_T9: all nine taps (convs), step s = tap T = 3*(dh+1) + (dw+1) = s
+//   UK_T6A / UK_T6B: a transposed-conv phase only has taps in two of the three columns, dw in {-1, 0} / {0, +1}: 6 steps instead of 9
+//          (no MFMAs on zero weights)
+//   UK_T6R: a two-column tap set whose side (A or B) is a run-time property of the tile (Conv3Args::ts_mask): numbered like UK_T6A, the
+//          column index T % 3 in {0, 1} then selects one of the tile's two column offsets instead of a fixed one
+//   UK_T3: 3 steps -- the three taps (dh, dw = 0) of the pair view (index 1 of the UK_T6A column numbering): an even-pixel chunk
+//   UK_P5: 5 steps -- k-step 0 of step s is tap 2s, k-step 1 tap 2s + 1 (tap 9: zero weights), both on the chunk's FIRST 16
+//          channels: a chunk with at most 16 real channels in 10 instead of 18 k-steps
+// The homogeneous forms are bodies of ONE unit: tap set TS = 0 -> [T9], 1 -> [T6A], 2 -> [T6B], 3 (all phases per launch) -> [T6R].
+// The heterogeneous ones (round 4, 8 x 32 tiles only) take out structural zeros of three layer classes:
 //   stride (1,2) on the pixel-pair view (rd_api.hip): the even pixel's 32-channel chunks only meet the three taps dw = 0, but ran
 //     all six pair-view taps (three of them on zero weights: 25 % of the layer's MFMAs);
 //   the 72-channel input of the level-0 tower convs / the 8-channel first layer: a chunk with <= 16 real channels ran two 16-channel
 //     k-steps per tap, one of them on zeros.
-// A BODY is a fixed cyclic sequence of up to four units of possibly different kinds; the tile runs it a.nchunk / NU times.  Every
-// compile-time table of the homogeneous form (tap of a step, halo pieces per step, counted waits) becomes a function of the GLOBAL
-// step index g within the body, evaluated cyclically (the step before step 0 is the body's last step: of the previous repetition
-// or of the previous tile).
-//   UK_T9 / UK_T6A / UK_T6B: the 9-tap and the two 6-tap units of the homogeneous forms (TS 0 / 1 / 2)
-//   UK_T3: 3 steps -- the three taps (dh, dw = 0) of the pair view (index 1 of the TS 1 column numbering): an even-pixel chunk
-//   UK_P5: 5 steps -- k-step 0 of step s is tap 2s, k-step 1 tap 2s + 1 (tap 9: zero weights), both on the chunk's FIRST 16
-//          channels: a chunk with at most 16 real channels in 10 instead of 18 k-steps
 // BODY 1 (stride 2), per 128-byte line of the view pixel: [T6A odd chunk | T3 even | T3 even | T6A odd] -- the chunk whose lines
 //   are new to L2 is always fetched during a 6-step unit, the 3-step units fetch the second half of a line that is already there;
 // BODY 2: [T9, T9, P5] (64 + <= 16 channels: the level-0 tower convs on [agg3 | range image]);  BODY 3: [P5] (the first layer).
@@ -251,28 +231,62 @@ constexpr C3KStep uk_kstep(int k, int s, int ks) {
   return C3KStep{T / 3, T % 3, ks};
 }
 struct C3Body { int nu; int kind[4]; };
-constexpr C3Body c3_body(int BODY) {
-  return BODY == 1 ? C3Body{4, {UK_T6A, UK_T3, UK_T3, UK_T6A}} : BODY == 2 ? C3Body{3, {UK_T9, UK_T9, UK_P5, 0}} : C3Body{1, {UK_P5, 0, 0, 0}};
+constexpr C3Body c3_body(int BODY, int TS = 0) {   // (BODY 1..3 fix their own kinds; TS describes the one unit of BODY 0)
+  return BODY == 1 ? C3Body{4, {UK_T6A, UK_T3, UK_T3, UK_T6A}} : BODY == 2 ? C3Body{3, {UK_T9, UK_T9, UK_P5, 0}}
+       : BODY == 3 ? C3Body{1, {UK_P5, 0, 0, 0}} : C3Body{1, {TS == 0 ? UK_T9 : TS == 1 ? UK_T6A : TS == 2 ? UK_T6B : UK_T6R, 0, 0, 0}};
 }
-constexpr int c3b_steps(int BODY) { int n = 0; for (int u = 0; u < c3_body(BODY).nu; ++u) n += uk_nsteps(c3_body(BODY).kind[u]); return n; }
-constexpr int c3b_unit(int BODY, int g) { int u = 0; while (g >= uk_nsteps(c3_body(BODY).kind[u])) { g -= uk_nsteps(c3_body(BODY).kind[u]); ++u; } return u; }
-constexpr int c3b_ord(int BODY, int g) { int u = 0; while (g >= uk_nsteps(c3_body(BODY).kind[u])) { g -= uk_nsteps(c3_body(BODY).kind[u]); ++u; } return g; }
-// halo pieces (wide tile: 6 per wave and unit) issued in step s of a unit with NS steps -- all of them early enough for the wait at
-// ordinal NS - 2 to cover them
-constexpr int uk_halo_pieces(int NS, int s) {
+constexpr int c3_nsteps(int TS) { return uk_nsteps(c3_body(0, TS).kind[0]); }   // (launcher) steps per unit of a tap set
+constexpr int c3_body_steps(C3Body bd) { int n = 0; for (int u = 0; u < bd.nu; ++u) n += uk_nsteps(bd.kind[u]); return n; }
+// Halo pieces a wave issues in step ordinal s of a unit with NS steps: Cfg::HPW in all, every one of them at least two steps before
+// the wait that must cover it (ordinal NS - 2).
+//   8 x 62 (10 per wave and unit): 2 each at ordinals 0..4 of a 9-step unit; 4, 4, 2 at ordinals 0..2 of a 6-step unit; no schedule
+//          (-1) for the 3- and 5-step units: bodies that contain them are 8 x 32 only (c3_schedule_ok, asserted by the kernel)
+//   8 x 32 (6 per wave and unit):  2, 1, 1, 1, 1 at ordinals 0..4 of a 9-step unit; 2 each at 0..2 of a 6-step unit; 3, 3 at 0..1 of
+//          a 5-step unit; all 6 at ordinal 0 of a 3-step unit.
+constexpr int c3_pieces(int NS, int s, C3Tile tile) {
+  if (tile == C3_8x62) return NS == 9 ? (s <= 4 ? 2 : 0) : NS == 6 ? (s <= 1 ? 4 : (s == 2 ? 2 : 0)) : -1;
   return NS == 9 ? (s == 0 ? 2 : s <= 4 ? 1 : 0) : NS == 6 ? (s <= 2 ? 2 : 0) : NS == 5 ? (s <= 1 ? 3 : 0) : (s == 0 ? 6 : 0);
 }
-constexpr int uk_halo_last(int NS) { return NS == 9 ? 4 : NS == 6 ? 2 : NS == 5 ? 1 : 0; }
-constexpr int c3b_pieces(int BODY, int g) { return uk_halo_pieces(uk_nsteps(c3_body(BODY).kind[c3b_unit(BODY, g)]), c3b_ord(BODY, g)); }
-constexpr int c3b_first(int BODY, int g) { int n = 0; for (int t = g - c3b_ord(BODY, g); t < g; ++t) n += c3b_pieces(BODY, t); return n; }
-// counted wait of global step g (c3_younger above, with the look-back running cyclically over the body)
-constexpr int c3b_younger(int BODY, int R, int IPW, int g) {
-  const int G = c3b_steps(BODY);
-  int n = (R - 3) * IPW;
-  for (int d = 1; d <= R - 2; ++d) n += c3b_pieces(BODY, ((g - d) % G + G) % G);
-  const int NS = uk_nsteps(c3_body(BODY).kind[c3b_unit(BODY, g)]), s = c3b_ord(BODY, g);
-  const int cap = (NS - 3 - uk_halo_last(NS)) * IPW;
-  return (s == NS - 2 && n > cap) ? cap : n;
+constexpr int c3_first(int NS, int s, C3Tile tile) { int n = 0; for (int t = 0; t < s; ++t) n += c3_pieces(NS, t, tile); return n; }   // pieces of a unit before ordinal s
+constexpr bool c3_schedule_ok(C3Body bd, C3Tile tile, int HPW) {   // every unit of the body has a schedule on this tile, HPW pieces long
+  for (int u = 0; u < bd.nu; ++u) {
+    int n = 0;
+    for (int s = 0; s < uk_nsteps(bd.kind[u]); ++s) {
+      if (c3_pieces(uk_nsteps(bd.kind[u]), s, tile) < 0) return false;
+      n += c3_pieces(uk_nsteps(bd.kind[u]), s, tile);
+    }
+    if (n != HPW) return false;
+  }
+  return true;
+}
+// Everything a step consumes at compile time, as a function of the GLOBAL step index g within the body, evaluated cyclically: the step
+// after the body's last one is its step 0, the one before step 0 its last (of the previous repetition or of the previous tile).
+struct C3Step {
+  C3KStep k1, kn;       // second k-step of this step; first k-step of the NEXT step (both are read during this step)
+  int pieces, first;    // halo pieces issued in this step and the index of the first of them among the unit's HPW
+  int wait;             // vmcnt of the step's counted wait (below)
+  bool ufirst, ulast;   // first / last step of its unit: the fetch cursor advances / the halo buffers swap
+};
+struct C3Pos { int kind, ns, s; };   // global step -> kind and step count of its unit, ordinal within it
+constexpr C3Pos c3_pos(C3Body bd, int g) {
+  int u = 0;
+  while (g >= uk_nsteps(bd.kind[u])) { g -= uk_nsteps(bd.kind[u]); ++u; }
+  return C3Pos{bd.kind[u], uk_nsteps(bd.kind[u]), g};
+}
+constexpr int c3_pieces_at(C3Body bd, int g, C3Tile tile) { return c3_pieces(c3_pos(bd, g).ns, c3_pos(bd, g).s, tile); }
+// The counted wait: DMA instructions a wave issues after "its part of slab g+2", as seen at the wait of step g: the halo pieces of
+// step g+2-R plus everything of steps g+3-R .. g-1.  Every step issues IPW slab instructions plus its halo pieces.  At ordinal NS-2
+// the wait must also cover the unit's last halo piece: the following step reads the next halo.
+constexpr C3Step c3_step(C3Body bd, int g, C3Tile tile, int R, int IPW) {
+  const int G = c3_body_steps(bd);
+  const C3Pos p = c3_pos(bd, g), pn = c3_pos(bd, (g + 1) % G);
+  int last = 0;   // ordinal of the unit's last piece
+  for (int s = 0; s < p.ns; ++s) if (c3_pieces(p.ns, s, tile) > 0) last = s;
+  int wait = (R - 3) * IPW;
+  for (int d = 1; d <= R - 2; ++d) wait += c3_pieces_at(bd, ((g - d) % G + G) % G, tile);
+  const int cap = (p.ns - 3 - last) * IPW;
+  if (p.s == p.ns - 2 && wait > cap) wait = cap;
+  return C3Step{uk_kstep(p.kind, p.s, 1), uk_kstep(pn.kind, pn.s, 0), c3_pieces(p.ns, p.s, tile), c3_first(p.ns, p.s, tile), wait, p.s == 0, p.s == p.ns - 1};
 }
 // unit i of a tile (i = 0 .. nchunk - 1 in program order) -> 32-channel chunk of the (view) input it reads
 __host__ __device__ inline int c3b_chunk(int BODY, int i, int nchunk) {
@@ -363,9 +377,10 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
   constexpr int C3_TW = Cfg::TW, C3_ROWB = Cfg::ROWB, RW = Cfg::RW;
   constexpr int NR = FPW + NCT;                  // fragment reads per k-step
   constexpr int NM = FPW * NCT;                  // MFMAs per k-step
-  constexpr int NS = c3_nsteps(TS);              // steps (taps) per unit (BODY 0)
-  constexpr int BG = BODY ? c3b_steps(BODY) : NS;          // steps of one repetition of the tile body
-  constexpr int BNU = BODY ? c3_body(BODY).nu : 1;         // units of one repetition
+  constexpr C3Body BD = c3_body(BODY, TS);       // the tile body: one unit for the homogeneous forms
+  constexpr int BG = c3_body_steps(BD);          // steps of one repetition of the tile body
+  constexpr int BNU = BD.nu;                     // units of one repetition
+  static_assert(c3_schedule_ok(BD, TILE, Cfg::HPW), "no halo-piece schedule for a unit of this body on this tile (3- and 5-step units: 8 x 32 only)");
   HIP_DYNAMIC_SHARED(unsigned char, smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 31, hi = lane >> 5;
@@ -536,7 +551,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     dma_v(ok ? (const void*)src : (const void*)a.zero16, buf + q * 1024);   // (buf = byte offset of the halo buffer)
   };
   int fslot = 0, fslab = 0;                               // ring slot / slab-within-tile of the NEXT slab to fetch
-  const int nslab_tile = BODY ? (a.nchunk / BNU) * BG : a.nchunk * NS;
+  const int nslab_tile = (a.nchunk / BNU) * BG;
   const unsigned char* wsrc = a.w;
   auto slab_piece = [&](int j) {
     dma_s(wsrc + (size_t)fslab * SLAB + (wave * IPW + j) * 1024, lane * 16, RING + fslot * SLAB + (wave * IPW + j) * 1024);
@@ -641,7 +656,7 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
   C3_SYNC(0, 0)
   C3_TRACE()
   // tap of the very first k-step (compile-time constants: a run-time evaluation of the body tables would put them on the stack)
-  constexpr C3KStep K00 = BODY ? uk_kstep(c3_body(BODY ? BODY : 3).kind[0], 0, 0) : C3KStep{c3_tap(TS, 0) / 3, c3_tap(TS, 0) % 3, 0};
+  constexpr C3KStep K00 = uk_kstep(BD.kind[0], 0, 0);
   constexpr int K00DW = K00.dw, K00DH = K00.dh;
   int rslot = 0;        // ring slot of the slab being consumed
   int abuf = 0;         // halo buffer (byte offset) of the unit being consumed
@@ -656,20 +671,28 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     C3_RD(0, k, C3_AO(K00DW) + abuf + K00DH * C3_ROWB, boff + rslot * SLAB, 0)
   }
 
-  // One step = tap T of the current unit, software pipelined by hand (one wave per SIMD: nothing else hides latency).
+  // Index of a step's first halo piece, where it is used: C3Step::first.  The one-unit forms spell it as the run-time call of a constexpr
+  // function that they always had: the optimiser folds it to the same constant, but hipcc then orders the two operands of one scalar add
+  // of the piece's LDS address the other way round in 14 instantiations (profiles/EXPERIMENTS.md).  Kept so that the code object stays
+  // the one that was measured; to be dropped by a change that is measured itself.
+#define C3_FIRST(D, G_) (BNU == 1 ? c3_first(BG, (G_), TILE) : (D).first)
+  // Global step G_ of the tile body (C3Step: every constant below comes from c3_step), software pipelined by hand (one wave per SIMD:
+  // nothing else hides latency).
   //   block 0: MFMAs of ks 0, with the reads of (this step, ks 1) interleaved 1:1 into its first half;
   //   block 1: MFMAs of ks 1, with the reads of (next step, ks 0) interleaved into its first half, then the step's
   //            barrier (slab g+2 landed everywhere, slab g free), then the DMA issue interleaved into the second half.
-#define C3_STEP(S) C3_STEP_(S, C3_MM)
-#define C3_STEP_(S, MM0)                                                                                             \
-  {                                                                                                                  \
-    constexpr int T_ = c3_tap(TS, (S)), TN_ = c3_tap(TS, ((S) + 1) % NS);                                            \
-    constexpr int dh_ = T_ / 3, dw_ = T_ % 3, ndh_ = TN_ / 3, ndw_ = TN_ % 3;                                        \
-    constexpr int NH_ = c3_halo_pieces((S), NS, TILE), NP_ = IPW + NH_;   /* DMA pieces of this step */                    \
-    const int acur_ = (C3_AO(dw_) + abuf + dh_ * C3_ROWB) ^ 32;                                                        \
+  // The fragment addresses carry the k-step's slot bit (C3_RD adds nothing for the pixel operand); the halo buffers swap after a
+  // unit's last step.  MM0 = C3_MMZ for the un-folded first step of a tile.
+#define C3_STEP(G_, MM0)                                                                                             \
+  if constexpr ((G_) < BG) {                                                                                         \
+    constexpr C3Step D_ = c3_step(BD, (G_), TILE, R, IPW);                                                           \
+    constexpr int NP_ = IPW + D_.pieces;   /* DMA pieces of this step */                                             \
+    const int acur_ = (C3_AO(D_.k1.dw) + abuf + D_.k1.dh * C3_ROWB) ^ (D_.k1.slot << 5);                             \
     const int bcur_ = boff + rslot * SLAB;                                                                           \
     const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = ((S) == NS - 1 && PH && lastc ? pq0 : C3_AO(ndw_)) + ((S) == NS - 1 ? hflip(abuf) : abuf) + ndh_ * C3_ROWB; \
+    int ncol_ = C3_AO(D_.kn.dw);                                                                                     \
+    if constexpr (PH && D_.ulast) { if (lastc) ncol_ = pq0; }   /* the tile's last step pre-reads the next list entry */\
+    const int anext_ = (ncol_ + (D_.ulast ? hflip(abuf) : abuf) + D_.kn.dh * C3_ROWB) ^ (D_.kn.slot << 5);           \
     const int bnext_ = boff + rnext_ * SLAB;                                                                         \
     const int hbuf_ = hflip(abuf);   /* the other buffer: unit u+1 */                                                 \
     C3_FENCE();                                                                                                      \
@@ -682,31 +705,37 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
       if (n < NR) C3_RD(0, n, anext_, bnext_, 0)                                                                     \
     }                                                                                                                \
     if (NR > NM / 2) { _Pragma("unroll") for (int n = NM / 2; n < NR; ++n) C3_RD(0, n, anext_, bnext_, 0) }          \
-    C3_SYNC(c3_younger(R, IPW, (S), NS, TILE), NR)                                                            \
-    if ((S) == 0) halo_begin();                                                                                      \
+    C3_SYNC(D_.wait, NR)                                                                                             \
+    if (D_.ufirst) halo_begin();                                                                                     \
     _Pragma("unroll") for (int n = NM / 2; n < NM; ++n) {                                                            \
       C3_MM(1, n)                                                                                                    \
       /* the step's DMA pieces, spread over the MFMA slots of this half block (slab pieces first) */                 \
       _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                                \
         if (p * (NM / 2) / NP_ == n - NM / 2) {                                                                      \
-          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                      \
+          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, C3_FIRST(D_, (G_)) + p - IPW);                          \
           C3_FENCE();                                                                                                \
         }                                                                                                            \
     }                                                                                                                \
     slab_advance();                                                                                                  \
     rslot = rnext_;                                                                                                  \
+    if (D_.ulast) abuf = hflip(abuf);                                                                                \
   }
+#define C3_BODY_FROM1 C3_STEP(1, C3_MM) C3_STEP(2, C3_MM) C3_STEP(3, C3_MM) C3_STEP(4, C3_MM) C3_STEP(5, C3_MM) C3_STEP(6, C3_MM)       \
+  C3_STEP(7, C3_MM) C3_STEP(8, C3_MM) C3_STEP(9, C3_MM) C3_STEP(10, C3_MM) C3_STEP(11, C3_MM) C3_STEP(12, C3_MM) C3_STEP(13, C3_MM)     \
+  C3_STEP(14, C3_MM) C3_STEP(15, C3_MM) C3_STEP(16, C3_MM) C3_STEP(17, C3_MM) C3_STEP(18, C3_MM) C3_STEP(19, C3_MM) C3_STEP(20, C3_MM)  \
+  C3_STEP(21, C3_MM) C3_STEP(22, C3_MM)
+  static_assert(BG <= 23, "C3_BODY_FROM1 unrolls 23 steps");
 
   // M16 step (see the kernel's header): block 0 with the reads of the slab's second half, block 1 with the reads of the next step
   // (weights first, a pixel half-fragment right after its last MFMA), the barrier after the first half of block 1 (6 reads of the next
-  // step outstanding), the DMA issue in its second half.
+  // step outstanding), the DMA issue in its second half.  Its own MFMA / read interleave; next tap, pieces and wait from c3_step.
 #define C3_STEP16(S)                                                                                                 \
   {                                                                                                                  \
-    constexpr int TN_ = c3_tap(TS, ((S) + 1) % NS), ndh_ = TN_ / 3, ndw_ = TN_ % 3;                                  \
-    constexpr int NH_ = c3_halo_pieces((S), NS, TILE), NP_ = IPW + NH_;                                               \
+    constexpr C3Step D_ = c3_step(BD, (S), TILE, R, IPW);                                                            \
+    constexpr int NP_ = IPW + D_.pieces;                                                                             \
     const int bcur_ = boff + rslot * SLAB;                                                                           \
     const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = aoff[ndw_] + ((S) == NS - 1 ? hflip(abuf) : abuf) + ndh_ * C3_ROWB;                           \
+    const int anext_ = aoff[D_.kn.dw] + (D_.ulast ? hflip(abuf) : abuf) + D_.kn.dh * C3_ROWB;                        \
     const int bnext_ = boff + rnext_ * SLAB;                                                                         \
     const int hbuf_ = hflip(abuf);                                                                                   \
     C3_FENCE();                                                                                                      \
@@ -720,13 +749,13 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
       if (n == 3) C3_RDP16(0, anext_)                                                                                \
       if (n == 7) C3_RDP16(1, anext_)                                                                                \
     }                                                                                                                \
-    C3_SYNC(c3_younger(R, IPW, (S), NS, TILE), 6)                                                                \
-    if ((S) == 0) halo_begin();                                                                                      \
+    C3_SYNC(D_.wait, 6)                                                                                              \
+    if (D_.ufirst) halo_begin();                                                                                     \
     _Pragma("unroll") for (int n = 8; n < 16; ++n) {                                                                 \
       C3_MM16(1, n)                                                                                                  \
       _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                                \
         if (p * 8 / NP_ == n - 8) {                                                                                  \
-          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, c3_halo_first((S), NS, TILE) + p - IPW);                 \
+          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, C3_FIRST(D_, (S)) + p - IPW);                           \
           C3_FENCE();                                                                                                \
         }                                                                                                            \
       if (n == 11) C3_RDP16(2, anext_)                                                                               \
@@ -734,53 +763,8 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
     }                                                                                                                \
     slab_advance();                                                                                                  \
     rslot = rnext_;                                                                                                  \
+    if (D_.ulast) abuf = hflip(abuf);                                                                                \
   }
-
-  // Global step g of a heterogeneous body: the same software pipeline as C3_STEP, with the tap / slot of each k-step, the halo
-  // pieces and the counted wait taken from the body's tables, and the halo buffer switched after a unit's last step.
-#define C3_GSTEP(G_, MM0)                                                                                            \
-  if constexpr (BODY != 0 && (G_) < BG) {                                                                            \
-    constexpr int U_ = c3b_unit(BODY, (G_)), S_ = c3b_ord(BODY, (G_)), K_ = c3_body(BODY).kind[U_], NSU_ = uk_nsteps(K_); \
-    constexpr int GN_ = ((G_) + 1) % BG, KN_ = c3_body(BODY).kind[c3b_unit(BODY, GN_)];                              \
-    constexpr C3KStep k1_ = uk_kstep(K_, S_, 1), kn_ = uk_kstep(KN_, c3b_ord(BODY, GN_), 0);                         \
-    constexpr bool lastS_ = S_ == NSU_ - 1;                                                                          \
-    constexpr int NH_ = c3b_pieces(BODY, (G_)), NP_ = IPW + NH_, HF_ = c3b_first(BODY, (G_)), YG_ = c3b_younger(BODY, R, IPW, (G_)); \
-    const int acur_ = (aoff[k1_.dw] + abuf + k1_.dh * C3_ROWB) ^ (k1_.slot << 5);                                    \
-    const int bcur_ = boff + rslot * SLAB;                                                                           \
-    const int rnext_ = rslot + 1 == R ? 0 : rslot + 1;                                                               \
-    const int anext_ = (aoff[kn_.dw] + (lastS_ ? hflip(abuf) : abuf) + kn_.dh * C3_ROWB) ^ (kn_.slot << 5);          \
-    const int bnext_ = boff + rnext_ * SLAB;                                                                         \
-    const int hbuf_ = hflip(abuf);                                                                                   \
-    C3_FENCE();                                                                                                      \
-    _Pragma("unroll") for (int n = 0; n < NM; ++n) {                                                                 \
-      MM0(0, n)                                                                                                      \
-      if (n < NR) C3_RDX(1, n, acur_, bcur_, 1)                                                                      \
-    }                                                                                                                \
-    _Pragma("unroll") for (int n = 0; n < NM / 2; ++n) {                                                             \
-      C3_MM(1, n)                                                                                                    \
-      if (n < NR) C3_RDX(0, n, anext_, bnext_, 0)                                                                    \
-    }                                                                                                                \
-    if (NR > NM / 2) { _Pragma("unroll") for (int n = NM / 2; n < NR; ++n) C3_RDX(0, n, anext_, bnext_, 0) }         \
-    C3_SYNC(YG_, NR)                                                                                                 \
-    if (S_ == 0) halo_begin();                                                                                       \
-    _Pragma("unroll") for (int n = NM / 2; n < NM; ++n) {                                                            \
-      C3_MM(1, n)                                                                                                    \
-      _Pragma("unroll") for (int p = 0; p < NP_; ++p)                                                                \
-        if (p * (NM / 2) / NP_ == n - NM / 2) {                                                                      \
-          if (p < IPW) slab_piece(p); else halo_piece(hbuf_, HF_ + p - IPW);                                         \
-          C3_FENCE();                                                                                                \
-        }                                                                                                            \
-    }                                                                                                                \
-    slab_advance();                                                                                                  \
-    rslot = rnext_;                                                                                                  \
-    if (lastS_) abuf = hflip(abuf);                                                                                  \
-  }
-  // (fragment read with an address that already carries the k-step's slot bit: C3_RD adds nothing for the pixel operand)
-#define C3_RDX(BUF, K, AADDR, BADDR, KS) C3_RD(BUF, K, AADDR, BADDR, KS)
-#define C3_GBODY_FROM1(MM) C3_GSTEP(1, MM) C3_GSTEP(2, MM) C3_GSTEP(3, MM) C3_GSTEP(4, MM) C3_GSTEP(5, MM) C3_GSTEP(6, MM) C3_GSTEP(7, MM) \
-  C3_GSTEP(8, MM) C3_GSTEP(9, MM) C3_GSTEP(10, MM) C3_GSTEP(11, MM) C3_GSTEP(12, MM) C3_GSTEP(13, MM) C3_GSTEP(14, MM) C3_GSTEP(15, MM)      \
-  C3_GSTEP(16, MM) C3_GSTEP(17, MM) C3_GSTEP(18, MM) C3_GSTEP(19, MM) C3_GSTEP(20, MM) C3_GSTEP(21, MM) C3_GSTEP(22, MM)
-  static_assert(BG <= 23, "C3_GBODY_FROM1 unrolls 23 steps");
 
   for (int k = 0; k < ntl; ++k) {
     if constexpr (PH) lastc = a.nchunk == 1;
@@ -814,10 +798,9 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
 #pragma unroll 1
       for (int c = 0; c < a.nchunk; ++c) {
         C3_STEP16(0) C3_STEP16(1) C3_STEP16(2) C3_STEP16(3) C3_STEP16(4) C3_STEP16(5) C3_STEP16(6) C3_STEP16(7) C3_STEP16(8)
-        abuf = hflip(abuf);
       }
     } else {
-    {   // first chunk of the tile, peeled: its first k-step starts the accumulators from C = 0 (FOLD: from the shift)
+    {   // first repetition of the body, peeled: its first k-step starts the accumulators from C = 0 (FOLD: from the shift)
       if constexpr (FOLD) {
         // (the zero words go through an opaque copy once per tile: as compile-time zeros the five operand tuples are loop
         //  invariant, hipcc keeps all 20 registers live across the MFMA phase, spills them, and reloads them here from scratch --
@@ -836,29 +819,16 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
           acc[n / NCT][n % NCT] = H16<DT>::mfma(bz, ones, f32x16{});
         }
         C3_FENCE();
-        if constexpr (BODY != 0) { C3_GSTEP(0, C3_MM) } else {
-        C3_STEP(0)
-        }
+        C3_STEP(0, C3_MM)
       } else {
-        C3_STEP_(0, C3_MMZ)
+        C3_STEP(0, C3_MMZ)
       }
-      if constexpr (BODY != 0) { C3_GBODY_FROM1(C3_MM) } else {
-      C3_STEP(1) C3_STEP(2) C3_STEP(3) C3_STEP(4) C3_STEP(5)
-      if constexpr (NS == 9) { C3_STEP(6) C3_STEP(7) C3_STEP(8) }
-      abuf = hflip(abuf);
-      }
+      C3_BODY_FROM1
     }
-    if constexpr (BODY != 0) {
 #pragma unroll 1
-      for (int c = BNU; c < a.nchunk; c += BNU) { C3_GSTEP(0, C3_MM) C3_GBODY_FROM1(C3_MM) }
-    } else {
-#pragma unroll 1
-    for (int c = 1; c < a.nchunk; ++c) {
+    for (int c = BNU; c < a.nchunk; c += BNU) {   // the remaining whole repetitions
       if constexpr (PH) lastc = c == a.nchunk - 1;
-      C3_STEP(0) C3_STEP(1) C3_STEP(2) C3_STEP(3) C3_STEP(4) C3_STEP(5)
-      if constexpr (NS == 9) { C3_STEP(6) C3_STEP(7) C3_STEP(8) }
-      abuf = hflip(abuf);
-    }
+      C3_STEP(0, C3_MM) C3_BODY_FROM1
     }
     }   // !M16
     if (k == 0) C3_TRACE()
@@ -1228,12 +1198,10 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
 #undef C3_MM16
 #undef C3_RDP16
 #undef C3_RDW16
-#undef C3_GBODY_FROM1
-#undef C3_RDX
-#undef C3_GSTEP
+#undef C3_BODY_FROM1
+#undef C3_FIRST
 #undef C3_AO
 #undef C3_STEP
-#undef C3_STEP_
 #undef C3_MMZ
 #undef C3_SYNC
 #undef C3_MM

@@ -204,7 +204,7 @@ def test_conv_fused_with_head_out_tile_switch(be):
     test_conv_fused_with_head_out(be, (1, 9, 1410, 32, 8))
 
 
-@pytest.mark.parametrize("be", BOTH, indirect=True)
+@pytest.mark.parametrize("be", WITH_LATE_DMA, indirect=True)
 @pytest.mark.parametrize("case", [(F32, 1, 3, 10, 128, 64, (3, 8), 4, 2), (BF16, 1, 2, 20, 128, 128, (3, 8), 4, 2),
                                   (F32, 2, 2, 13, 64, 64, (3, 4), 2, 1), (BF16, 1, 3, 24, 128, 64, (3, 4), 2, 1),
                                   (F16, 1, 2, 20, 128, 128, (3, 8), 4, 2), (F16, 1, 3, 24, 128, 64, (3, 4), 2, 1)])
@@ -846,7 +846,7 @@ def test_conv3x3_ex_folded_scale_fp16(be, case):
     run_conv_ex(be, *case, seed=sum(v or 0 for v in case[:6]), fold=True, dt=F16)
 
 
-@pytest.mark.parametrize("be", BOTH, indirect=True)
+@pytest.mark.parametrize("be", WITH_LATE_DMA, indirect=True)
 @pytest.mark.parametrize("case", [(BF16, 2, 9, 70, 64, 8, 16, 128), (BF16, 1, 17, 40, 32, 8, 16, 64), (F16, 2, 9, 70, 64, 8, 16, 128), (BF16, 1, 8, 33, 64, 24, 24, 128)])
 def test_conv3x3_cat_two_tensor_input(be, case):
     """rd_conv3x3_bn_act_cat: 3x3 conv + BN + ReLU over the channel concatenation [x1 | x2] of two tensors with their own channel
