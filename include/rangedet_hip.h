@@ -30,6 +30,7 @@
  *   rd_train_transform        training-time input chain: the same plus Bbox3dAssigner, GenerateTarget and the training
  *                             FPN targets                                         rangedet/core/input.py:276-320,323-519,522-624,
  *                                                                                 operator_cxx/src_cxx/assigner.h:11-109
+ *   rd_range_image_from_points  get_range_image + range_image_mask                datasets/create_range_image_in_kitti.py:107-137,178
  *
  * Conventions
  *   - every function returns an int status (RD_OK == 0, negative = error); nothing aborts or exits.
@@ -441,6 +442,30 @@ int rd_train_transform(const float* range_image, const float* pc_vehicle_frame, 
                        const float* gt_limits, const float* gt_bbox_csa, const int* num_gt_host, int Mmax, float radius,
                        float max_dist, const float* reg_weight_host, int B, int H, int W, int Hp, int Wp,
                        const rd_train_outputs_t* out_host, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- range image from a raw spinning-LiDAR point cloud (the step before rd_input_transform for data that ships no range image) ----
+ * datasets/create_range_image_in_kitti.py:107-137 (get_range_image) and :178 (range_image_mask), for B scans of different lengths in one
+ * call.  points (sum N_b, 4) float32 x, y, z, intensity, scan b = rows [offsets_host[b], offsets_host[b+1]); incl_host / height_host: H
+ * doubles each, the beams' inclinations and sensor heights (read on the host at call time, like offsets_host).  Per point, in the
+ * reference's arithmetic:
+ *   row    = first arg-min over beams i of |incl[i] - atan2(height[i] - z, xy_norm)| in double, xy_norm = sqrtf(x*x + y*y) (float)
+ *   column = float throughout: round-half-even((W - 0.5) - (atan2f(y, x) + pi) / (2 pi) * W), then == W -> W - 1, < 0 -> 0 (the reference
+ *            hard-codes W = 2048); atan2f is the C library's (glibc / fdlibm) bit for bit
+ *   range  = sqrtf((x*x + y*y) + z*z)
+ * The nearest point of a cell wins (the reference writes in order of decreasing range).  TIE RULE: of two points of one cell with the
+ * same range the one with the HIGHER index wins -- what a stable argsort gives; the reference's argsort is not stable, so it leaves this
+ * open.  A point with a non-finite x, y or z (outside the reference's contract) is skipped; nothing is ever written out of bounds.
+ * Outputs: range_image (B,H,W,5) float32 = [range, x, y, z, intensity] of the winning point, five -1 in an empty cell; mask (B,H,W)
+ * bytes 0/1 = range_image[..., 0] > -1; point_index (B,H,W) int32 = the winner's index within its scan, -1 = empty (may be NULL).
+ * ws: B*H*W*8 bytes of keys, set on the stream in every call (its contents on entry do not matter).  points and range_image must be
+ * 16-byte aligned, ws 8-byte aligned.  The result does not depend on the order in which the GPU processes the points.
+ * RD_ESHAPE: B < 1, H outside 1..128, W outside 1..2^22, offsets_host not non-decreasing from 0, a scan of 2^31 points or more.
+ * RD_EWORKSPACE: ws_bytes < rd_range_image_workspace_bytes(B, H, W).  RD_EINVAL: a null required pointer (points may be NULL only when
+ * there is no point at all), a misaligned buffer.  A scan without points is valid: all -1. */
+size_t rd_range_image_workspace_bytes(int B, int H, int W);
+int rd_range_image_from_points(const float* points, const long long* offsets_host, int B, const double* incl_host,
+                               const double* height_host, int H, int W, float* range_image, unsigned char* mask, int* point_index,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

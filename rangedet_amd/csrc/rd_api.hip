@@ -5,6 +5,7 @@
 #include "k_assign.h"
 #include "k_input.h"
 #include "k_target.h"
+#include "k_rangeimg.h"
 #include "k_nms3d.h"
 #include "k_meta.h"
 #include "k_misc.h"
@@ -1045,6 +1046,48 @@ int rd_train_transform(const float* range_image, const float* pc_vehicle_frame, 
     hipLaunchKernelGGL(train_write_kernel, dim3((unsigned)(((long)Hp * Wp + 255) / 256), nb), dim3(256), 0, st, a);
   }
   return check_launch("train_transform");
+}
+
+// ---- range image from a raw point cloud (k_rangeimg.h) ------------------------------------------------------------------
+size_t rd_range_image_workspace_bytes(int B, int H, int W) {
+  return B > 0 && H > 0 && W > 0 ? (size_t)B * H * W * sizeof(unsigned long long) : 0;
+}
+int rd_range_image_from_points(const float* points, const long long* offsets_host, int B, const double* incl_host,
+                               const double* height_host, int H, int W, float* range_image, unsigned char* mask, int* point_index,
+                               void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(offsets_host && incl_host && height_host && range_image && mask && ws, RD_EINVAL, "range_image_from_points: null pointer");
+  RD_REQUIRE(B >= 1 && H >= 1 && H <= RI_MAX_BEAMS && W >= 1 && W <= RI_MAX_WIDTH, RD_ESHAPE,
+             "range_image_from_points: B %d, H %d (1..%d), W %d (1..%d)", B, H, RI_MAX_BEAMS, W, RI_MAX_WIDTH);
+  RD_REQUIRE(offsets_host[0] == 0, RD_ESHAPE, "range_image_from_points: offsets[0] = %lld, not 0", offsets_host[0]);
+  for (int b = 0; b < B; ++b) {
+    const long long n = offsets_host[b + 1] - offsets_host[b];
+    RD_REQUIRE(n >= 0 && n < (1LL << 31), RD_ESHAPE, "range_image_from_points: scan %d has %lld points (0..2^31-1)", b, n);
+  }
+  RD_REQUIRE(points || offsets_host[B] == 0, RD_EINVAL, "range_image_from_points: null points");
+  RD_REQUIRE(((uintptr_t)points | (uintptr_t)range_image) % 16 == 0 && (uintptr_t)ws % 8 == 0, RD_EINVAL,
+             "range_image_from_points: points and range_image must be 16-byte aligned, the workspace 8-byte aligned");
+  const size_t need = rd_range_image_workspace_bytes(B, H, W);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "range_image_from_points: workspace %zu < %zu bytes", ws_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(ws, 0xFF, need, st) != hipSuccess) return fail(RD_EHIP, "range_image_from_points: memset failed");   // every key = RI_EMPTY
+  RangeImgArgs a;
+  a.points = points; a.key = (unsigned long long*)ws;
+  a.range_image = range_image; a.mask = mask; a.point_index = point_index;
+  a.H = H; a.W = W;
+  for (int r = 0; r < RI_MAX_BEAMS; ++r) { a.incl[r] = r < H ? incl_host[r] : 0.0; a.height[r] = r < H ? height_host[r] : 0.0; }
+  ProfScope ps(RD_PROF_LAYOUT, st);
+  const unsigned cell_blocks = (unsigned)(((long long)H * W + 255) / 256);
+  for (int b0 = 0; b0 < B; b0 += RI_SCANS_PER_LAUNCH) {
+    const int nb = std::min(RI_SCANS_PER_LAUNCH, B - b0);
+    long long nchunk = 0;
+    for (int i = 0; i <= RI_SCANS_PER_LAUNCH; ++i) a.off[i] = offsets_host[b0 + std::min(i, nb)];
+    for (int i = 0; i < nb; ++i) nchunk = std::max(nchunk, a.off[i + 1] - a.off[i]);
+    a.b0 = b0;
+    if (nchunk > 0)
+      hipLaunchKernelGGL(range_image_project_kernel, dim3((unsigned)((nchunk + 255) / 256), nb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(range_image_resolve_kernel, dim3(cell_blocks, nb), dim3(256), 0, st, a);
+  }
+  return check_launch("range_image_from_points");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------
