@@ -30,6 +30,8 @@
  *   rd_train_transform        training-time input chain: the same plus Bbox3dAssigner, GenerateTarget and the training
  *                             FPN targets                                         rangedet/core/input.py:276-320,323-519,522-624,
  *                                                                                 operator_cxx/src_cxx/assigner.h:11-109
+ *   rd_rpn_loss               get_iou_target + get_vfl_loss + get_normalize_reg_loss of one level, with the gradients MakeLoss sends
+ *                             back                                                head/builder.py:156-196,268-422, head/loss.py:4-30
  *   rd_range_image_from_points  get_range_image + range_image_mask                datasets/create_range_image_in_kitti.py:107-137,178
  *
  * Conventions
@@ -466,6 +468,41 @@ size_t rd_range_image_workspace_bytes(int B, int H, int W);
 int rd_range_image_from_points(const float* points, const long long* offsets_host, int B, const double* incl_host,
                                const double* height_host, int H, int W, float* range_image, unsigned char* mask, int* point_index,
                                void* ws, size_t ws_bytes, void* stream);
+
+/* ---- RPN loss head of one pyramid level: IoU target, varifocal loss, normalised smooth-L1 loss and their head gradients ----------
+ * RangeRpnHead.get_iou_target / get_vfl_loss / get_normalize_reg_loss (rangedet/symbol/head/builder.py:156-196,350-422, called per level
+ * by get_fpn_loss :268-348) with vari_focal_loss (rangedet/symbol/head/loss.py:4-30), one class, iou_type 'bev'.  n = H * Wl, pixel
+ * i = h * Wl + w in every layout (builder.py:122-141).  With x = logit, s = IoU target, m = mask, float32:
+ *   s         = max over the frame's n_gt boxes of the cleaned (NaN / Inf / > 1 / < 0 -> 0) 8-point IoU of the box decoded from the
+ *               pixel's deltas (rd_decode3d_bbox, is_bin = 0) -- for every pixel, the mask does not enter; behind block_grad
+ *   norm_cls  = float(sum of mask over the batch) + 1, norm_reg = float(sum of reg_norm_weight over the batch) + 1 (:366,411)
+ *   p = 1 / (1 + expf(-x)), Lp = logf(clip(p, 1e-6f, 1 - 1e-6f)), Lm = -x [x >= 0] - log1pf(expf(x - 2 x [x >= 0]))
+ *   L0 = -(0.5 s Lp + 0.5 (1 - s) Lm) * 2;  vfl = L0 s (s > 0), L0 alpha |s - p|^gamma (s == 0);  cls_loss = vfl m / norm_cls
+ *   x_r = delta - target, sigma = smooth_l1_scalar: sl1 = 0.5 sigma^2 x_r^2 (|x_r| < 1 / sigma^2), else |x_r| - 0.5 / sigma^2; |x_r| with l1
+ *   reg_loss  = sl1 reg_weight reg_norm_weight / norm_reg * reg_loss_weight; channel c of pixel i pairs delta[b,i,c] with target[b,c,h,w]
+ * and what MakeLoss (grad_scale, :374-378,417-421) sends back, c = [1e-6f <= p <= 1 - 1e-6f], dL0 = -(s c (1 - p) - (1 - s) p):
+ *   d_logit   = scale_loss_shift cls_loss_weight m / norm_cls * (s dL0 (s > 0);  alpha (dL0 p^gamma + L0 gamma p^(gamma-1) p (1 - p)) (s == 0))
+ *   d_delta   = scale_loss_shift reg_loss_weight reg_weight reg_norm_weight / norm_reg * (sigma^2 x_r inside, sign(x_r) outside or with l1)
+ * The loss maps are not scaled by grad_scale (MakeLoss forward is the identity).  The batch strides (in floats) let a level be a slice
+ * of the forward's flat (B,N) / (B,N,8) buffers (rd_head_out): pass base + n_off [* 8] and N [* 8].  p_host is read on the host at call
+ * time.  stats: 4 floats on the device = norm_cls, norm_reg, sum(cls_loss), sum(reg_loss); every sum is accumulated in double in a fixed
+ * order (no atomics), so two calls give the same bits.  All launches go on `stream`, nothing synchronises; the contents of ws on entry
+ * do not matter.  d_logit, d_delta, iou_target and boxes10 (the decoded boxes, a diagnostic) may be NULL.
+ * RD_ESHAPE: B < 1 or > 65535, H < 1, Wl < 1, n_gt outside 1..256, logit_bstride < n, delta_bstride < 8 n, delta_bstride % 4 != 0.
+ * RD_EINVAL: a null required pointer, delta / d_delta not 16-byte aligned, ws not 8-byte aligned, smooth_l1_scalar <= 0.
+ * RD_EWORKSPACE: ws_bytes < rd_rpn_loss_workspace_bytes(B, n).  Every check precedes the first launch. */
+typedef struct {            /* read on the host at call time */
+  float alpha, gamma;                       /* config:123-124 (1, 2) */
+  float cls_loss_weight, reg_loss_weight;   /* config:126,125 (10, 8) */
+  float smooth_l1_scalar;                   /* config:129 (3); MXNet smooth_l1: sigma = scalar */
+  float scale_loss_shift;                   /* config:36,115 with builder.py:97: 128 in fp16 mode, else 1 */
+  int l1;                                   /* builder.py:397-401: |x| instead of smooth_l1 */
+} rd_loss_param_t;
+size_t rd_rpn_loss_workspace_bytes(int B, long n);
+int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long delta_bstride, const float* pc, const float* gt_bbox,
+                int n_gt, const float* mask, const float* reg_target, const float* reg_weight, const float* reg_norm_weight, int B, int H,
+                int Wl, const rd_loss_param_t* p_host, float* cls_loss, float* reg_loss, float* d_logit, float* d_delta,
+                float* iou_target, float* boxes10, float* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

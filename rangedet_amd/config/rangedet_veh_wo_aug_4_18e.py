@@ -274,3 +274,20 @@ def get_train_transform(variant="veh", feat_size=(64, 2650), pad_field=(64, 2656
         ["pc_vehicle_frame_s{}".format(s) for s in strides] + ['gt_bbox_{}_for_iou_pred'.format(V["class_names"][0])] + \
         ['coord_s1']                                                                           # config:369-378
     return transform, data_name, label_name
+
+
+def get_loss_param(fp16=True):
+    """The reference's ``RpnParam.loss`` (config:122-129) with the ``scale_loss_shift`` the head applies to it (config:36,115 with
+    builder.py:97: 128 in fp16 mode, else 1): what ``rangedet_amd.loss.RpnLoss`` takes.  The same for the veh / ped variants."""
+    _shift = 128.0 if fp16 else 1.0
+
+    class loss:
+        alpha = 1
+        gamma = 2
+        reg_loss_weight = 8
+        cls_loss_weight = 10
+        iou_type = 'bev'
+        smooth_l1_scalar = 3
+        scale_loss_shift = _shift
+
+    return loss

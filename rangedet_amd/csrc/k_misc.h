@@ -194,12 +194,9 @@ __global__ __launch_bounds__(256) void head_out_mfma_kernel(const bf16_t* __rest
 // ---- Decode3DBbox  (decode_3d_bbox-inl.h:64-277) ------------------------------------------------------------
 // One thread per point: 44 B in, 40 B out.  Same operation order as the reference's Map(); the two spots where
 // the reference's float instantiation goes through double (0.5*length, height/2.0) do so here too.
-__global__ __launch_bounds__(256) void decode3d_kernel(const float* __restrict__ delta, const float* __restrict__ pc,
-                                                       float* __restrict__ out, long n, int box_type, int is_bin) {
-  long idx = blockIdx.x * 256L + threadIdx.x;
-  if (idx >= n) return;
-  const float* d = delta + idx * box_type;
-  float pc_x = pc[idx * 3 + 0], pc_y = pc[idx * 3 + 1], pc_z = pc[idx * 3 + 2];
+// decode3d_box: one point.  d = the point's deltas, o = the 10 output floats (global memory or registers); the k_loss.h kernel decodes
+// with it in registers.
+__device__ __forceinline__ void decode3d_box(const float* d, float pc_x, float pc_y, float pc_z, int is_bin, float* o) {
   float az = atan2f(pc_y, pc_x);
   float ca = cosf(az), sa = sinf(az);
   float dx, dy, width, length, height, z0, yaw_l;
@@ -228,7 +225,6 @@ __global__ __launch_bounds__(256) void decode3d_kernel(const float* __restrict__
   float hl = (float)(0.5 * (double)length), hw = (float)(0.5 * (double)width);
   float hx[4] = {hl, -hl, -hl, hl};
   float hy[4] = {-hw, -hw, hw, hw};
-  float* o = out + idx * 10;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     o[2 * k] = (hx[k] * cyw - hy[k] * sy) + cx;
@@ -236,6 +232,12 @@ __global__ __launch_bounds__(256) void decode3d_kernel(const float* __restrict__
   }
   o[8] = z0;
   o[9] = z0 + height;
+}
+__global__ __launch_bounds__(256) void decode3d_kernel(const float* __restrict__ delta, const float* __restrict__ pc,
+                                                       float* __restrict__ out, long n, int box_type, int is_bin) {
+  long idx = blockIdx.x * 256L + threadIdx.x;
+  if (idx >= n) return;
+  decode3d_box(delta + idx * box_type, pc[idx * 3 + 0], pc[idx * 3 + 1], pc[idx * 3 + 2], is_bin, out + idx * 10);
 }
 
 // ---- score filter + 10->11 dim  (tools/test.py:56-81,200-209) --------------------------------------------------

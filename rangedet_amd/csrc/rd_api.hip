@@ -10,6 +10,7 @@
 #include "k_meta.h"
 #include "k_misc.h"
 #include "k_riou.h"
+#include "k_loss.h"
 #include "k_sort.h"
 #include "k_wnms.h"
 
@@ -1088,6 +1089,43 @@ int rd_range_image_from_points(const float* points, const long long* offsets_hos
     hipLaunchKernelGGL(range_image_resolve_kernel, dim3(cell_blocks, nb), dim3(256), 0, st, a);
   }
   return check_launch("range_image_from_points");
+}
+
+// ---- RPN loss head of one level (k_loss.h) -------------------------------------------------------------------------------
+size_t rd_rpn_loss_workspace_bytes(int B, long n) { return B > 0 && B <= 65535 && n > 0 ? loss_ws_bytes(B, n) : 0; }
+int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long delta_bstride, const float* pc, const float* gt_bbox,
+                int n_gt, const float* mask, const float* reg_target, const float* reg_weight, const float* reg_norm_weight, int B, int H,
+                int Wl, const rd_loss_param_t* p_host, float* cls_loss, float* reg_loss, float* d_logit, float* d_delta,
+                float* iou_target, float* boxes10, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(logit && delta && pc && gt_bbox && mask && reg_target && reg_weight && reg_norm_weight && p_host && cls_loss && reg_loss &&
+                 stats && ws, RD_EINVAL, "rpn_loss: null pointer");
+  RD_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && Wl >= 1, RD_ESHAPE, "rpn_loss: B %d (1..65535), H %d, Wl %d", B, H, Wl);
+  RD_REQUIRE(n_gt >= 1 && n_gt <= 256, RD_ESHAPE, "rpn_loss: n_gt %d (1..256; the config pads to 200)", n_gt);
+  const long n = (long)H * Wl;
+  RD_REQUIRE(logit_bstride >= n && delta_bstride >= 8 * n && delta_bstride % 4 == 0, RD_ESHAPE,
+             "rpn_loss: batch strides %ld (>= %ld) and %ld (>= %ld, a multiple of 4)", logit_bstride, n, delta_bstride, 8 * n);
+  RD_REQUIRE(((uintptr_t)delta | (uintptr_t)d_delta) % 16 == 0 && (uintptr_t)ws % 8 == 0, RD_EINVAL,
+             "rpn_loss: delta and d_delta must be 16-byte aligned, the workspace 8-byte aligned");
+  RD_REQUIRE(p_host->smooth_l1_scalar > 0.f, RD_EINVAL, "rpn_loss: smooth_l1_scalar %g (> 0)", (double)p_host->smooth_l1_scalar);
+  const size_t need = rd_rpn_loss_workspace_bytes(B, n);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "rpn_loss: workspace %zu < %zu bytes", ws_bytes, need);
+  LossArgs a;
+  a.logit = logit; a.delta = delta; a.pc = pc; a.gt = gt_bbox; a.mask = mask;
+  a.reg_target = reg_target; a.reg_weight = reg_weight; a.reg_norm_weight = reg_norm_weight;
+  a.logit_bs = logit_bstride; a.delta_bs = delta_bstride; a.n = n; a.B = B; a.ngt = n_gt;
+  a.p = *p_host;
+  a.cls_loss = cls_loss; a.reg_loss = reg_loss; a.d_logit = d_logit; a.d_delta = d_delta; a.iou_target = iou_target; a.boxes10 = boxes10;
+  a.stats = stats;
+  a.norm_blocks = loss_norm_blocks(B, n);
+  const long npix = loss_pixel_blocks(B, n);
+  a.part_mask = (double*)ws; a.part_nw = a.part_mask + a.norm_blocks;
+  a.part_cls = a.part_nw + a.norm_blocks; a.part_reg = a.part_cls + npix;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(loss_norm_kernel, dim3(a.norm_blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, a.part_mask, a.part_nw, (long)a.norm_blocks, 1.0f, stats);
+  hipLaunchKernelGGL(loss_pixel_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, a.part_cls, a.part_reg, npix, 0.0f, stats + 2);
+  return check_launch("rpn_loss");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------

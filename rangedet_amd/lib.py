@@ -131,6 +131,9 @@ SIGNATURES = {
     "rd_range_image_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rd_range_image_from_points": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_void_p]),
+    "rd_rpn_loss_workspace_bytes": (c_size_t, [c_int, c_long]),
+    "rd_rpn_loss": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_int, c_int]
+                    + [c_void_p] * 9 + [c_size_t, c_void_p]),
     "rd_prof_enable": (c_int, [c_int]),
     "rd_prof_reset": (c_int, []),
     "rd_prof_get": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_long)]),

@@ -1,7 +1,8 @@
 """``RangeRCNN`` / ``RangeRpnHead`` -- the inference half of rangedet/symbol/head/builder.py with the reference's
 method surface: RangeRCNN.get_test_symbol :54-77; RangeRpnHead.sep_level_type :99-154, get_fpn_output :198-266,
 get_fpn_prediction :424-479, get_prediction_of_one_type :481-534.  The training half (get_train_symbol,
-get_fpn_loss, get_iou_target, loss symbols) is out of scope and raises NotImplementedError.
+get_fpn_loss, get_iou_target, loss symbols) is out of scope as a graph and raises NotImplementedError; what the loss methods
+compute (:156-196,268-422) runs on the device in ``rangedet_amd.loss.RpnLoss``, outside the symbol graph.
 """
 from ... import mx
 from ... import mxnext as X
@@ -90,7 +91,8 @@ class RangeRpnHead(object):
         return cls_d, reg_d
 
     def get_fpn_loss(self, *args, **kwargs):
-        raise NotImplementedError("training graph is outside the hot path this package implements")
+        raise NotImplementedError("the loss is not recorded as a symbol graph; rangedet_amd.loss.RpnLoss computes the IoU target, the "
+                                  "losses and their head gradients on the device from the head outputs and the training inputs")
 
     get_iou_target = get_vfl_loss = get_normalize_reg_loss = get_fpn_loss
 
