@@ -1213,17 +1213,9 @@ __global__ __launch_bounds__(256, (TILE == C3_8x32 ? 2 : 1)) void conv3x3_stream
 // Build options (none is set by rangedet_amd.build; tests/emu/build_emu.sh passes both to keep the CPU emulation of the persistent
 // kernels small and its compile time in minutes):
 //   -DRD_BUILD_NUM_CUS=n                     workgroup slots are sized for n compute units instead of asking the device
+//                                            (conv_num_cus, rd_common.h)
 //   -DRD_BUILD_F16_PRODUCTION_FORMS_ONLY     fp16: only the launch forms the lowering emits (folded scales on the two-workgroup
 //                                            tiles, fused output conv); other fp16 shapes take the generic tap kernel
-inline int conv_num_cus() {
-#ifdef RD_BUILD_NUM_CUS
-  return RD_BUILD_NUM_CUS;
-#else
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-  return v;
-#endif
-}
 
 // One launch of one instantiation; the first launch of each raises its dynamic-LDS limit (once per process and instantiation).
 template <int NCT, int TS, bool HEAD, bool SC, bool FOLD, C3Tile TILE, int DT, int BODY = 0, bool M16 = false>

@@ -10,11 +10,11 @@
 // element-wise product, exactly the B operand of MFMA #2 -- the channel <-> (lane,reg) permutation this needs
 // is baked into the packed weights on the host (rd_pack_meta_host), giving each lane 16 CONTIGUOUS channels
 // per 32-channel block (wide LDS reads / global stores).
-//   workgroup = WAVES waves = WAVES rows x 32 columns, persistent over tiles; LDS: bf16 weights (108 KiB),
-//   per-tap constants, and the (WAVES+2) x 34 data halo (XOR-swizzled 16-byte slots).
-//   meta_kernel<RD_F32> (parity mode): v_mfma_f32_32x32x2_f32, hidden layer on the VALU, weights streamed from L2
-//   (220 KiB > LDS).  meta_bf16_kernel (production, end of this file): hidden layer on the matrix cores too.
-// INPUT CONTRACT: data and coordinates are FINITE.  The 16-bit production form (meta16_kernel<8, DT, 219>) applies its ReLUs as a packed
+//   workgroup = META_WAVES (8) waves = 8 rows x 32 columns, persistent over tiles; the LDS regions of both kernels are
+//   Meta16Lds / Meta32Lds below, their launch is launch_meta at the end of this file.
+//   meta_kernel (fp32, parity mode): v_mfma_f32_32x32x2_f32, hidden layer on the VALU, weights streamed from L2 (220 KiB > LDS).
+//   meta16_kernel<RD_BF16 | RD_F16> (production): hidden layer on the matrix cores too, weights and both halos in LDS.
+// INPUT CONTRACT: data and coordinates are FINITE.  The 16-bit production kernel (meta16_kernel) applies its ReLUs as a packed
 // signed 16-bit max on the converted values and splits coordinates into a high + low part: for finite inputs that is bit-identical to
 // relu(x) = x > 0 ? x : 0, but a positive-signed NaN survives the integer max (the reference's relu maps NaN to 0) and an Inf / fp16
 // overflow in a coordinate difference makes the low part NaN.  rd_input_transform (k_input.h) produces finite values by
@@ -23,14 +23,16 @@
 #pragma once
 #include "rd_common.h"
 
+#include <algorithm>
+
 namespace rd {
 
 struct MetaLayout {  // byte offsets inside the packed parameter block
   size_t w1s, a2, b1p, t1, w0p, s2t2, w0f, total;
   size_t wbytes;  // w1s + a2 (the part held in LDS for bf16)
 };
-__host__ __device__ inline MetaLayout meta_layout(int dt) {
-  MetaLayout L;
+__host__ __device__ constexpr MetaLayout meta_layout(int dt) {
+  MetaLayout L{};
   const bool h = dt != RD_F32;   // RD_BF16 / RD_F16: 16-bit weights in MFMA-fragment order
   const size_t w1s = h ? 9 * 2 * 2 * 64 * 16 : 9 * 2 * 4 * 64 * 16;
   const size_t a2 = h ? 9 * 2 * 2 * 2 * 64 * 16 : 9 * 2 * 2 * 4 * 64 * 16;
@@ -143,6 +145,33 @@ inline void pack_meta(const float* w0, const float* b0, const float* w1, const f
   }
 }
 
+// ---- workgroup shape and LDS layout (read by the kernels and by launch_meta) ------------------------------------------------------
+// A workgroup is META_WAVES waves: wave = one row of 32 pixels of an 8 x 32 tile, whose halo is 10 rows x 34 columns.  With the 16-bit
+// weights in LDS no other wave count has ever fitted the 160 KiB (12 waves: a 14-row halo of 61 KB next to 108 KB of weights).
+constexpr int META_WAVES = 8;
+constexpr int META_HR = META_WAVES + 2, META_HC = 34;   // halo rows / columns
+// Both kernels copy the per-tap constants b1 [9][64], t1 [9][64], W0 (fp32 form) [2][16][4] and s2 / t2 [2][64] out of the packed block
+// (MetaLayout b1p .. w0f) in one piece.
+struct Meta16Lds {   // meta16_kernel: byte offsets and sizes; PXB = bytes of one halo pixel (64 channels)
+  static constexpr int PXB = 128;
+  static constexpr size_t W_B = meta_layout(RD_BF16).wbytes;                                 // W1 + A fragments, 108 KiB
+  static constexpr size_t CONST_B = meta_layout(RD_BF16).w0f - meta_layout(RD_BF16).b1p;     // 5.5 KiB
+  static constexpr size_t HALO_B = (size_t)META_HR * META_HC * PXB;                          // 42.5 KiB
+  static constexpr size_t CHALO_B = 4096;                                                    // coordinates [3][HR][HC] fp32
+  static constexpr size_t WEIGHTS = 0, CONSTS = WEIGHTS + W_B, HALO = CONSTS + CONST_B, CHALO = HALO + HALO_B, TOTAL = CHALO + CHALO_B;
+};
+static_assert(meta_layout(RD_F16).wbytes == Meta16Lds::W_B && meta_layout(RD_F16).w0f == meta_layout(RD_BF16).w0f,
+              "the two 16-bit types share one packed layout");
+static_assert(3 * META_HR * META_HC * sizeof(float) <= Meta16Lds::CHALO_B, "meta16_kernel: the coordinate halo exceeds its LDS region");
+static_assert(Meta16Lds::TOTAL == 160 * 1024, "meta16_kernel takes the whole 160 KiB of a compute unit: one workgroup per CU");
+struct Meta32Lds {   // meta_kernel (fp32): constants and data halo; the weights stream from L2, the coordinates from global memory
+  static constexpr int PXB = 256;
+  static constexpr size_t CONST_B = meta_layout(RD_F32).w0f - meta_layout(RD_F32).b1p;
+  static constexpr size_t HALO_B = (size_t)META_HR * META_HC * PXB;
+  static constexpr size_t CONSTS = 0, HALO = CONSTS + CONST_B, TOTAL = HALO + HALO_B;
+};
+static_assert(Meta32Lds::TOTAL == 92672, "meta_kernel (fp32): LDS total");
+
 struct MetaArgs {
   const void* data; int d_cs, d_co;
   const float* coord;  // NCHW (B,3,H,W)
@@ -177,51 +206,45 @@ __device__ __forceinline__ void meta_tile(const MetaArgs& a, int v, int& tw, int
 #endif
 }
 
-template <int DT, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void meta_kernel(MetaArgs a) {
-  static_assert(DT == RD_F32, "the 16-bit types run meta16_kernel (its packed W0 / W1 layouts differ); this is the fp32 parity kernel");
-  using E = Elem<DT>;
-  using T = typename E::T;
-  constexpr int PXB = 256;             // bytes per pixel (64 channels)
-  constexpr int SPP = PXB / 16;        // 16-byte slots per pixel
-  constexpr int HC = 34;               // halo columns
+// ---- fp32 parity kernel ---------------------------------------------------------------------------------------------
+// The 16-bit types run meta16_kernel (its packed W0 / W1 layouts differ).  Tiles in the plain order (column tile fastest).
+__global__ __launch_bounds__(META_WAVES * 64) void meta_kernel(MetaArgs a) {
+  using L = Meta32Lds;
+  constexpr int PXB = L::PXB;          // bytes per pixel (64 channels)
+  constexpr int SPP = PXB / 16;        // 16-byte slots per pixel (4 channels each)
+  constexpr int HC = META_HC, HR = META_HR, NT = META_WAVES * 64;
   HIP_DYNAMIC_SHARED(unsigned char, smem);
-  // LDS carve: [consts] [halo]; the weights (220 KiB) stream from L2
-  constexpr size_t W1S_B = 9 * 2 * 4 * 64 * 16;
-  constexpr size_t A2_B = 9 * 2 * 2 * 4 * 64 * 16;
-  constexpr size_t WB = W1S_B + A2_B;
-  constexpr size_t CONST_B = 9 * 64 * 4 * 2 + 512 + 512;
-  unsigned char* lc = smem;                       // consts
-  unsigned char* halo = lc + CONST_B;
+  constexpr MetaLayout P = meta_layout(RD_F32);
+  unsigned char* lc = smem + L::CONSTS;
+  unsigned char* halo = smem + L::HALO;
   const float* cb1 = (const float*)lc;            // [9][64]
   const float* ct1 = cb1 + 9 * 64;                // [9][64]
   const float* cw0 = ct1 + 9 * 64;                // [2][16][4]
   const float* cs2 = cw0 + 2 * 16 * 4;            // [64] s2, [64] t2
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int px = lane & 31, hi = lane >> 5;
-  const int NT = WAVES * 64;
 
-  for (size_t i = tid; i < CONST_B / 16; i += NT) ((Slot16*)lc)[i] = ((const Slot16*)(a.packed + WB))[i];
-  const unsigned char* w1s = a.packed;
-  const unsigned char* a2w = w1s + W1S_B;
+  for (size_t i = tid; i < L::CONST_B / 16; i += NT) ((Slot16*)lc)[i] = ((const Slot16*)(a.packed + P.b1p))[i];
+  const unsigned char* w1s = a.packed + P.w1s;
+  const unsigned char* a2w = a.packed + P.a2;
 
-  const T* data = (const T*)a.data;
-  T* yout = (T*)a.y;
+  const float* data = (const float*)a.data;
+  float* yout = (float*)a.y;
   const long HW = (long)a.H * a.W;
 
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const int tw = tile % a.tiles_w;
     const int th = (tile / a.tiles_w) % a.tiles_h;
     const int b = tile / (a.tiles_w * a.tiles_h);
-    const int h0 = th * WAVES, w0 = tw * 32;
+    const int h0 = th * META_WAVES, w0 = tw * 32;
     __syncthreads();
-    for (int idx = tid; idx < (WAVES + 2) * HC * SPP; idx += NT) {
+    for (int idx = tid; idx < HR * HC * SPP; idx += NT) {
       const int pl = idx / SPP, s = idx - pl * SPP;
       const int r = pl / HC, c = pl - r * HC;
       const int ih = h0 - 1 + r, iw = w0 - 1 + c;
       Slot16 v = {0u, 0u, 0u, 0u};
       if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-        v = *(const Slot16*)(data + (((size_t)b * a.H + ih) * a.W + iw) * a.d_cs + a.d_co + s * E::CH);
+        v = *(const Slot16*)(data + (((size_t)b * a.H + ih) * a.W + iw) * a.d_cs + a.d_co + s * 4);
       *(Slot16*)(halo + pl * PXB + ((s ^ (pl & 15)) << 4)) = v;
     }
     __syncthreads();
@@ -308,78 +331,65 @@ __global__ __launch_bounds__(WAVES * 64) void meta_kernel(MetaArgs a) {
     }
     // epilogue: BN + ReLU, 16 contiguous output channels per (lane, ot)
     if (live) {
-      T* yp = yout + (((size_t)b * a.H + h) * a.W + w) * a.y_cs + a.y_co;
+      float* yp = yout + (((size_t)b * a.H + h) * a.W + w) * a.y_cs + a.y_co;
 #pragma unroll
       for (int ot = 0; ot < 2; ++ot) {
         const int ob = 32 * ot + 16 * hi;
-        T tmp[16];
+        float tmp[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          tmp[r] = E::from_f32(fmaxf(acc2[ot][r] * cs2[ob + r] + cs2[64 + ob + r], 0.f));
-        Slot16 pk[sizeof(T)];  // 16 elements = sizeof(T) slots of 16 bytes
+          tmp[r] = fmaxf(acc2[ot][r] * cs2[ob + r] + cs2[64 + ob + r], 0.f);
+        Slot16 pk[4];  // 16 floats = 4 slots of 16 bytes
         memcpy(pk, tmp, sizeof(tmp));
 #pragma unroll
-        for (int i = 0; i < (int)sizeof(T); ++i) *(Slot16*)(yp + ob + i * E::CH) = pk[i];
+        for (int i = 0; i < 4; ++i) *(Slot16*)(yp + ob + i * 4) = pk[i];
       }
     }
   }
 }
 
 
-// ---- bf16 production kernel ----------------------------------------------------------------------------------------
-// Same math as meta_kernel<RD_BF16>, restructured so that the vector ALU is no longer the bottleneck:
-//   * the 3 -> 32 hidden layer runs on the matrix cores as ONE bf16 MFMA on high/low split operands (error 2^-18, see
+// ---- 16-bit production kernel ---------------------------------------------------------------------------------------
+// Same math as meta_kernel, restructured so that the vector ALU is no longer the bottleneck:
+//   * the 3 -> 32 hidden layer runs on the matrix cores as ONE 16-bit MFMA on high/low split operands (error 2^-18, see
 //     pack_meta; the two v_mfma_f32_32x32x2_f32 it replaces cost 128 of the ~510 MFMA cycles of a tap);
 //     its D layout IS the B operand of MFMA #1 (the hidden-unit permutation is baked into the packed W1);
-//   * the element-wise stage uses packed fp32 FMAs, packed bf16 conversion and an integer packed max as ReLU;
+//   * the element-wise stage uses packed fp32 FMAs, packed 16-bit conversion and an integer packed max as ReLU;
 //   * point coordinates come from an LDS halo (one coalesced fetch per tile instead of 27 global loads per pixel);
 //   * the next tile's data / coordinate halo is fetched into registers while the current tile is computed.
-// LDS: weights 108 KiB + constants 5.5 KiB + data halo 42.5 KiB + coordinate halo 4 KiB = 160 KiB, one workgroup per CU.
+// LDS (Meta16Lds): weights 108 KiB + constants 5.5 KiB + data halo 42.5 KiB + coordinate halo 4 KiB = 160 KiB, one workgroup per CU.
 // DT = RD_BF16 or RD_F16 (same structure; the high / low split of MFMA #0 then carries 2^-18 resp. 2^-24 relative error).
-// V: form of the tap loop (bit flags; every combination computes bit-identical results -- tools/micro/meta_v_bench.py checks that on
-// the GPU and times them side by side, profiles/EXPERIMENTS.md round 4).  V = 0 is the plain loop of rounds 2 - 4a:
-//   1   explicit software pipeline: the two MFMA #1 of (tap, block) step n + 1 are issued before the element-wise stage of step n
-//   2   ... and the hidden layer (MFMA #0 + ReLU + pack) of tap k + 2 during block 1 of tap k
-//   4   ... with a scheduling fence (vector / matrix instructions may not cross) between the look-ahead group and the current step
-//   8   halo fetch addresses as 32-bit offsets from 24-bit multiplies (no 64-bit / quarter-rate integer multiplies per tile)
-//   16  both fragments of a block are converted first, then its four MFMA #2 are issued together
-//   32  MFMA #1 two steps ahead (three dynamic-weight buffers)
-//   64  the epilogue's ReLU as a packed 16-bit integer max after the conversion (16 instead of 32 instructions)
-//   128 hidden-layer operand without the two per-tap selects of the upper lane half (its k-slots 12 .. 15 meet zero weights)
-// (Forms measured and removed again -- the commit "Meta-Kernel: tap loop as an explicit software pipeline" has them: 256 / 512 timing
-//  ablations without the per-tap constant reads / with two vector instructions per pair; 1024 the neighbour's 16-bit channels converted
-//  to fp32 by an MFMA with a 0 / 1 permutation matrix, exact and bit-identical but 240 us.)
-// META_FORM = 219 (1 + 2 + 8 + 16 + 64 + 128) is what rd_meta_kernel_fwd launches: 210 - 215 us against 225 - 227 us for V = 0 on the same
-// boxes (gpurun_out/r4m4, r4m5).  What did NOT pay: the fence (4), two steps of look-ahead (32), the conversion MFMA (1024: 240 us --
-// every added MFMA sits in a step's dependent chain and costs ~80 wave cycles, 2.5 x its pipe time).
-constexpr int META_FORM = 219;
-template <int WAVES, int DT = RD_BF16, int V = META_FORM>
-__global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
-  static_assert((V & ~0x1FF) == 0, "meta16_kernel: unknown form flag");
-  // 256 (round 6 experiment, harness only -- tools/micro/meta_w12.hip): the 36 KB of W1 fragments are read from global memory (L2 / L1
-  // resident, every wave of the chip reads the same 4 KB per tap) instead of LDS, which frees the LDS a 12-wave workgroup needs for its
-  // 14-row halo: three waves per SIMD at <= 168 registers instead of two ("the W1-ring + third-wave form")
-  constexpr bool W1G = (V & 256) != 0;
+// The nine taps are 18 fully unrolled steps (tap k, 32-channel block mt) of an explicit three-stage software pipeline -- tap offsets,
+// weight and constant addresses are immediates of the LDS instructions:
+//   hidden(k)      MFMA #0 + ReLU + pack of tap k, issued during step (k - 2, 1): two taps ahead, into the buffer hf[k & 1] that
+//                  d1calc(k - 2, 1) has just read for the last time
+//   d1calc(k, mt)  the two MFMA #1 of step n + 1, issued before the element-wise stage of step n
+//   elem(k, mt)    element-wise stage of step n: both fragments of the block are converted first, then its four MFMA #2 go out together
+// 210 - 215 us against 225 - 227 us for the plain tap loop on the same boxes.  Every MFMA added to a step sits in its dependent
+// MFMA -> vector -> MFMA chain and costs ~80 wave cycles, 2.5 x its pipe time; the forms that did not pay (a scheduling fence between
+// the stages, MFMA #1 two steps ahead, W1 read from global memory for 12-wave workgroups, a conversion MFMA, float ReLUs, 64-bit halo
+// addresses) are in profiles/EXPERIMENTS.md, their code in the parent of the commit that made this kernel one form.
+template <int DT>
+__global__ __launch_bounds__(META_WAVES * 64) void meta16_kernel(MetaArgs a) {
   using HT = H16<DT>;
+  using L = Meta16Lds;
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   typedef short s16x2 __attribute__((ext_vector_type(2)));
-  constexpr int PXB = 128, SPP = 8, HC = 34, HR = WAVES + 2, NT = WAVES * 64;
+  constexpr int PXB = L::PXB, SPP = PXB / 16, HC = META_HC, HR = META_HR, NT = META_WAVES * 64;
   HIP_DYNAMIC_SHARED(unsigned char, smem);
-  constexpr size_t W1S_B = 9 * 2 * 2 * 64 * 16, A2_B = 9 * 2 * 2 * 2 * 64 * 16, WB = W1S_B + A2_B;
-  constexpr size_t CONST_B = 9 * 64 * 4 * 2 + 512 + 512;
-  constexpr size_t WBL = W1G ? A2_B : WB;         // weight bytes held in LDS
-  unsigned char* lw = smem;
-  unsigned char* lc = smem + WBL;
-  unsigned char* halo = lc + CONST_B;
-  float* chalo = (float*)(halo + HR * HC * PXB);  // [3][HR][HC]
+  constexpr MetaLayout P = meta_layout(DT);
+  unsigned char* lw = smem + L::WEIGHTS;
+  unsigned char* lc = smem + L::CONSTS;
+  unsigned char* halo = smem + L::HALO;
+  float* chalo = (float*)(smem + L::CHALO);       // [3][HR][HC]
   const float* cb1 = (const float*)lc;            // [9][64]
   const float* ct1 = cb1 + 9 * 64;                // [9][64]
   const float* cs2 = ct1 + 9 * 64 + 2 * 16 * 4;   // [64] s2, [64] t2
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int px = lane & 31, hi = lane >> 5;
 
-  for (size_t i = tid; i < WBL / 16; i += NT) ((Slot16*)lw)[i] = ((const Slot16*)(a.packed + (W1G ? W1S_B : 0)))[i];
-  for (size_t i = tid; i < CONST_B / 16; i += NT) ((Slot16*)lc)[i] = ((const Slot16*)(a.packed + WB))[i];
+  for (size_t i = tid; i < L::W_B / 16; i += NT) ((Slot16*)lw)[i] = ((const Slot16*)a.packed)[i];
+  for (size_t i = tid; i < L::CONST_B / 16; i += NT) ((Slot16*)lc)[i] = ((const Slot16*)(a.packed + P.b1p))[i];
   const bf16_t* data = (const bf16_t*)a.data;
   bf16_t* yout = (bf16_t*)a.y;
   const long HW = (long)a.H * a.W;
@@ -408,29 +418,27 @@ __global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
     crow[u] = (short)(pl / HC); ccol[u] = (short)(pl - (pl / HC) * HC);
     cch[u] = idx < CITEMS ? ch : -1;
   }
+  // Per-image offsets are 32-bit, built from 24-bit multiplies (no 64-bit / quarter-rate integer multiplies per tile); launch_meta
+  // refuses the images that would not fit.
   auto fetch = [&](int tile) {
     int tw, th, b;
     meta_tile(a, tile, tw, th, b);
-    const int h0 = th * WAVES - 1, w0 = tw * 32 - 1;
+    const int h0 = th * META_WAVES - 1, w0 = tw * 32 - 1;
     const bf16_t* dbase = data + (size_t)b * a.H * a.W * a.d_cs;
     const float* cbase = a.coord + (size_t)b * 3 * HW;
 #pragma unroll
     for (int u = 0; u < DU; ++u) {
       const int ih = h0 + drow[u], iw = w0 + dcol[u];
       dreg[u] = Slot16{0u, 0u, 0u, 0u};
-      if (dlds[u] >= 0 && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-        if constexpr (V & 8) dreg[u] = *(const Slot16*)(dbase + (size_t)(unsigned)(__mul24(__mul24(ih, a.W) + iw, a.d_cs) + dsrc[u]));
-        else dreg[u] = *(const Slot16*)(dbase + ((size_t)ih * a.W + iw) * a.d_cs + dsrc[u]);
-      }
+      if (dlds[u] >= 0 && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
+        dreg[u] = *(const Slot16*)(dbase + (size_t)(unsigned)(__mul24(__mul24(ih, a.W) + iw, a.d_cs) + dsrc[u]));
     }
 #pragma unroll
     for (int u = 0; u < CU; ++u) {
       const int ih = h0 + crow[u], iw = w0 + ccol[u];
       creg[u] = 0.f;                              // im2col zero padding: outside the image the coordinate is 0
-      if (cch[u] >= 0 && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-        if constexpr (V & 8) creg[u] = cbase[(size_t)(unsigned)(__mul24(cch[u], (int)HW) + __mul24(ih, a.W) + iw)];
-        else creg[u] = cbase[(size_t)cch[u] * HW + (long)ih * a.W + iw];
-      }
+      if (cch[u] >= 0 && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
+        creg[u] = cbase[(size_t)(unsigned)(__mul24(cch[u], (int)HW) + __mul24(ih, a.W) + iw)];
     }
   };
   auto commit = [&]() {
@@ -443,25 +451,25 @@ __global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
   };
 
   // A operand of the hidden-layer MFMA (see pack_meta): four registers for the whole kernel
-  const s16x8 w0frag = *(const s16x8*)(a.packed + meta_layout(DT).w0f + lane * 16);
+  const s16x8 w0frag = *(const s16x8*)(a.packed + P.w0f + lane * 16);
   // per-lane LDS addresses that do not depend on the tile: everything a tap adds to them is a compile-time constant
-  const unsigned char* w1l;                                  // + ((k*2 + mt)*2 + ks) * 1024
-  if constexpr (W1G) w1l = a.packed + lane * 16; else w1l = lw + lane * 16;
-  const unsigned char* a2l = lw + (W1G ? 0 : W1S_B) + lane * 16;   // + (((k*2 + ot)*2 + mt)*2 + s2) * 1024
+  const unsigned char* w1l = lw + P.w1s + lane * 16;         // + ((k*2 + mt)*2 + ks) * 1024
+  const unsigned char* a2l = lw + P.a2 + lane * 16;          // + (((k*2 + ot)*2 + mt)*2 + s2) * 1024
   const float* cbl = cb1 + 16 * hi;                          // + k*64 + 32*mt + 4*q
   const float* ctl = ct1 + 16 * hi;
   const int pl0 = (wv + 1) * HC + (px + 1);                  // centre pixel of this lane in the halo
+
   int tile = blockIdx.x;
   if (tile < a.ntiles) fetch(tile);
   for (; tile < a.ntiles; tile += gridDim.x) {
     int tw, th, b;
     meta_tile(a, tile, tw, th, b);
-    const int h0 = th * WAVES, w0 = tw * 32;
+    const int h0 = th * META_WAVES, w0 = tw * 32;
     __syncthreads();          // every wave is done with the previous tile's halos (and the weights are in place)
     commit();
     __syncthreads();
     if (tile + (int)gridDim.x < a.ntiles) fetch(tile + gridDim.x);   // in flight during this tile's math
-    // (issuing it at tap 3 instead -- 214 instead of 240 registers -- changes nothing: 272 vs 272 us, gpurun_out/r3zg)
+    // (issuing it at tap 3 instead -- 214 instead of 240 registers -- changes nothing: 272 vs 272 us)
 
     const int h = h0 + wv, w = w0 + px;
     const bool live = (h < a.H) && (w < a.W);
@@ -473,157 +481,22 @@ __global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[ot][r] = 0.f;
 
-    if constexpr (V & 1) {
-      // the same arithmetic as the loop below (bit-identical results), as three stages of an explicit software pipeline
-      auto hidden = [&](int k, s16x8 (&hf)[2]) {
-        const int pl = pl0 + (k / 3 - 1) * HC + (k % 3 - 1);
-        const float r0 = chalo[pl] - c0, r1 = chalo[HR * HC + pl] - c1, r2 = chalo[2 * HR * HC + pl] - c2;
-        const unsigned hxy = HT::pk(r0, r1), hz1 = HT::pk(r2, 1.0f);
-        const f32x2 uxy = HT::unpk(hxy), uz1 = HT::unpk(hz1);
-        const float l0 = r0 - uxy[0], l1 = r1 - uxy[1];
-        const float l2 = r2 - uz1[0];
-        const unsigned lxy = HT::pk(l0, l1), lz0 = HT::pk(l2, 0.f);
-        // (128: no selects -- k-slots 12 .. 15 of the upper lane half meet zero weights in the A operand, pack_meta, so what they hold
-        //  does not matter as long as it is finite, and the low parts are)
-        unsigned pk0[4] = {hxy, hz1, (V & 128) || !hi ? lxy : 0u, (V & 128) || !hi ? lz0 : 0u};
-        s16x8 b0frag;
-        memcpy(&b0frag, pk0, 16);
-        const f32x16 pre = HT::mfma(w0frag, b0frag, f32x16{});
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          unsigned pk[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned v = HT::pk(pre[8 * ks + 2 * e], pre[8 * ks + 2 * e + 1]);
-            pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-          }
-          memcpy(&hf[ks], pk, 16);
-        }
-      };
-      auto d1calc = [&](int k, int mt, const s16x8 (&hf)[2]) {
-        f32x16 d1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 bq = *(const f32x4*)(cbl + k * 64 + 32 * mt + 4 * q);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d1[4 * q + e] = bq[e];
-        }
-        if (k != META_CENTRE_TAP) {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            const s16x8 af = *(const s16x8*)(w1l + ((k * 2 + mt) * 2 + ks) * 1024);
-            d1 = HT::mfma(af, hf[ks], d1);
-          }
-        }
-        return d1;
-      };
-      auto elem = [&](int k, int mt, const f32x16& d1) {
-        const int pl = pl0 + (k / 3 - 1) * HC + (k % 3 - 1);
-        const unsigned char* hp = halo + pl * PXB;
-        const int swz = (pl >> 1) & 7;
-        s16x8 bfr[2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const Slot16 dv = *(const Slot16*)(hp + (((4 * mt + 2 * hi + s2) ^ swz) << 4));
-          const f32x4 t0 = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2);
-          const f32x4 t1v = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2 + 4);
-          unsigned pk[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const f32x2 x2 = HT::unpk(dv[e]);
-            const f32x2 w2 = {d1[8 * s2 + 2 * e], d1[8 * s2 + 2 * e + 1]};
-            const f32x2 b2 = e < 2 ? f32x2{t0[2 * e], t0[2 * e + 1]} : f32x2{t1v[2 * e - 4], t1v[2 * e - 3]};
-            const f32x2 v2 = x2 * w2 + b2;
-            const unsigned v = HT::pk(v2[0], v2[1]);
-            pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-          }
-          memcpy(&bfr[s2], pk, 16);
-          if constexpr (!(V & 16)) {
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot) {
-              const s16x8 af = *(const s16x8*)(a2l + (((k * 2 + ot) * 2 + mt) * 2 + s2) * 1024);
-              acc2[ot] = HT::mfma(af, bfr[s2], acc2[ot]);
-            }
-          }
-        }
-        if constexpr (V & 16) {   // both fragments of the block first, then its four MFMA #2
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot) {
-              const s16x8 af = *(const s16x8*)(a2l + (((k * 2 + ot) * 2 + mt) * 2 + s2) * 1024);
-              acc2[ot] = HT::mfma(af, bfr[s2], acc2[ot]);
-            }
-        }
-      };
-      s16x8 hf[2][2] = {};
-      if constexpr (V & 32) {
-        // MFMA #1 TWO steps ahead (three dynamic-weight buffers), the hidden layer a whole tap ahead of that
-        f32x16 d1c[3];
-        hidden(0, hf[0]);
-        hidden(1, hf[1]);
-        d1c[0] = d1calc(0, 0, hf[0]);
-        d1c[1] = d1calc(0, 1, hf[0]);
-#pragma unroll
-        for (int st = 0; st < 18; ++st) {
-          const int k = st >> 1, mt = st & 1;
-          if (st + 2 < 18) {
-            const int k2 = (st + 2) >> 1;       // = k + 1, block mt
-            d1c[(st + 2) % 3] = d1calc(k2, mt, hf[k2 & 1]);
-          }
-          elem(k, mt, d1c[st % 3]);
-          // hf[k & 1] was last read by d1calc(k, 1), issued at step (k - 1, 1): free from step (k, 0) on; tap k + 2 goes in at (k, 1)
-          if (mt == 1 && k + 2 < 9 && k + 2 != META_CENTRE_TAP) hidden(k + 2, hf[k & 1]);
-        }
-      } else {
-      f32x16 d1b[2];
-      hidden(0, hf[0]);
-      if constexpr (V & 2) hidden(1, hf[1]);
-      d1b[0] = d1calc(0, 0, hf[0]);
-#pragma unroll
-      for (int st = 0; st < 18; ++st) {
-        const int k = st >> 1, mt = st & 1;
-        if (st + 1 < 18) {
-          const int k2 = (st + 1) >> 1, mt2 = (st + 1) & 1;
-          if constexpr (V & 2) {   // hidden layer two steps ahead: tap k + 2's after the last use of the buffer (tap k, block 1)
-          } else if (mt2 == 0 && k2 != META_CENTRE_TAP) hidden(k2, hf[k2 & 1]);
-          d1b[(st + 1) & 1] = d1calc(k2, mt2, hf[k2 & 1]);
-          if constexpr (V & 4) __builtin_amdgcn_sched_barrier(0x94);   // scalar / memory instructions may cross, vector / matrix ones may not
-        }
-        elem(k, mt, d1b[st & 1]);
-        if constexpr (V & 2) {
-          // buffer hf[k & 1] is free once d1calc(k, 1) has been issued, i.e. after step (k, 0): tap k + 2 goes in during step (k, 1)
-          if (mt == 1 && k + 2 < 9 && k + 2 != META_CENTRE_TAP) hidden(k + 2, hf[k & 1]);
-        }
-      }
-      }
-    } else {
-    // the nine taps, fully unrolled: tap offsets, weight / constant addresses are immediates of the LDS instructions
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      constexpr int dummy = 0; (void)dummy;
-      const int dh = k / 3 - 1, dw = k % 3 - 1;
-      const int pl = pl0 + dh * HC + dw;
-      // (centre tap: rel = 0 for every pixel, the dynamic weight is the per-channel constant pack_meta put into the bias slot:
-      //  no hidden layer, no MFMA #1 -- 5 of the 117 MFMAs and ~30 of the ~1000 vector instructions of a pixel fragment)
-      const bool centre = k == META_CENTRE_TAP;
-      f32x16 pre = f32x16{};
-      s16x8 hfrag[2] = {};
-      if (!centre) {
+    // MFMA #0: pre[j][px] = W0[j][0..2] . rel + b0[j], one 16-bit MFMA on high / low split operands (~fp32 accurate); then the hidden
+    // vector as the two B fragments of MFMA #1 (ReLU on the packed pairs: a negative 16-bit float is a negative int16)
+    auto hidden = [&](int k, s16x8 (&hf)[2]) {
+      const int pl = pl0 + (k / 3 - 1) * HC + (k % 3 - 1);
       const float r0 = chalo[pl] - c0, r1 = chalo[HR * HC + pl] - c1, r2 = chalo[2 * HR * HC + pl] - c2;
-      // MFMA #0: pre[j][px] = W0[j][0..2] . rel + b0[j], one bf16 MFMA on high / low split operands (~fp32 accurate)
-      {
-        const unsigned hxy = HT::pk(r0, r1), hz1 = HT::pk(r2, 1.0f);
-        const f32x2 uxy = HT::unpk(hxy), uz1 = HT::unpk(hz1);
-        const float l0 = r0 - uxy[0], l1 = r1 - uxy[1];
-        const float l2 = r2 - uz1[0];
-        const unsigned lxy = HT::pk(l0, l1), lz0 = HT::pk(l2, 0.f);
-        unsigned pk0[4] = {hxy, hz1, hi ? 0u : lxy, hi ? 0u : lz0};
-        s16x8 b0frag;
-        memcpy(&b0frag, pk0, 16);
-        pre = HT::mfma(w0frag, b0frag, f32x16{});
-      }
-      // hidden vector as the two B fragments of MFMA #1 (ReLU on the packed pairs: negative bf16 = negative int16)
+      const unsigned hxy = HT::pk(r0, r1), hz1 = HT::pk(r2, 1.0f);
+      const f32x2 uxy = HT::unpk(hxy), uz1 = HT::unpk(hz1);
+      const float l0 = r0 - uxy[0], l1 = r1 - uxy[1];
+      const float l2 = r2 - uz1[0];
+      const unsigned lxy = HT::pk(l0, l1), lz0 = HT::pk(l2, 0.f);
+      // (no select that zeroes the low parts in the upper lane half: its k-slots 12 .. 15 meet zero weights in the A operand, pack_meta,
+      //  so what they hold does not matter as long as it is finite, and the low parts are)
+      unsigned pk0[4] = {hxy, hz1, lxy, lz0};
+      s16x8 b0frag;
+      memcpy(&b0frag, pk0, 16);
+      const f32x16 pre = HT::mfma(w0frag, b0frag, f32x16{});
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         unsigned pk[4];
@@ -632,57 +505,79 @@ __global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
           const unsigned v = HT::pk(pre[8 * ks + 2 * e], pre[8 * ks + 2 * e + 1]);
           pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
         }
-        memcpy(&hfrag[ks], pk, 16);
+        memcpy(&hf[ks], pk, 16);
       }
+    };
+    // MFMA #1: D1[ch][px] = (s1 W1)[ch][:] . relu(pre)[:] + s1*b1, one 32-channel block at a time
+    // (centre tap: rel = 0 for every pixel, the dynamic weight is the per-channel constant pack_meta put into the bias slot:
+    //  no hidden layer, no MFMA #1 -- 5 of the 117 MFMAs and ~30 of the ~1000 vector instructions of a pixel fragment)
+    auto d1calc = [&](int k, int mt, const s16x8 (&hf)[2]) {
+      f32x16 d1;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 bq = *(const f32x4*)(cbl + k * 64 + 32 * mt + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d1[4 * q + e] = bq[e];
       }
-      const unsigned char* hp = halo + pl * PXB;
-      const int swz = (pl >> 1) & 7;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        // MFMA #1: D1[ch][px] = (s1 W1)[ch][:] . relu(pre)[:] + s1*b1, one 32-channel block at a time
-        f32x16 d1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 bq = *(const f32x4*)(cbl + k * 64 + 32 * mt + 4 * q);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d1[4 * q + e] = bq[e];
-        }
-        if (!centre) {
+      if (k != META_CENTRE_TAP) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const s16x8 af = *(const s16x8*)(w1l + ((k * 2 + mt) * 2 + ks) * 1024);
-          d1 = HT::mfma(af, hfrag[ks], d1);
-        }
-        }
-        // element-wise: a = relu(data[p+d] * d1 + t1), channels 32mt+16hi+r of the neighbour pixel (from the halo)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const Slot16 dv = *(const Slot16*)(hp + (((4 * mt + 2 * hi + s2) ^ swz) << 4));
-          const f32x4 t0 = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2);
-          const f32x4 t1v = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2 + 4);
-          unsigned pk[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const f32x2 x2 = HT::unpk(dv[e]);
-            const f32x2 w2 = {d1[8 * s2 + 2 * e], d1[8 * s2 + 2 * e + 1]};
-            const f32x2 b2 = e < 2 ? f32x2{t0[2 * e], t0[2 * e + 1]} : f32x2{t1v[2 * e - 4], t1v[2 * e - 3]};
-            const f32x2 v2 = x2 * w2 + b2;
-            const unsigned v = HT::pk(v2[0], v2[1]);
-            pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-          }
-          s16x8 bfrag;
-          memcpy(&bfrag, pk, 16);
-          // MFMA #2: acc2[o][px] += A[o][(ch,k)] . a[ch]
-#pragma unroll
-          for (int ot = 0; ot < 2; ++ot) {
-            const s16x8 af = *(const s16x8*)(a2l + (((k * 2 + ot) * 2 + mt) * 2 + s2) * 1024);
-            acc2[ot] = HT::mfma(af, bfrag, acc2[ot]);
-          }
+          d1 = HT::mfma(af, hf[ks], d1);
         }
       }
+      return d1;
+    };
+    // element-wise: a = relu(data[p+d] * d1 + t1), channels 32mt+16hi+r of the neighbour pixel (from the halo), then
+    // MFMA #2: acc2[o][px] += A[o][(ch,k)] . a[ch]
+    auto elem = [&](int k, int mt, const f32x16& d1) {
+      const int pl = pl0 + (k / 3 - 1) * HC + (k % 3 - 1);
+      const unsigned char* hp = halo + pl * PXB;
+      const int swz = (pl >> 1) & 7;
+      s16x8 bfr[2];
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const Slot16 dv = *(const Slot16*)(hp + (((4 * mt + 2 * hi + s2) ^ swz) << 4));
+        const f32x4 t0 = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2);
+        const f32x4 t1v = *(const f32x4*)(ctl + k * 64 + 32 * mt + 8 * s2 + 4);
+        unsigned pk[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const f32x2 x2 = HT::unpk(dv[e]);
+          const f32x2 w2 = {d1[8 * s2 + 2 * e], d1[8 * s2 + 2 * e + 1]};
+          const f32x2 b2 = e < 2 ? f32x2{t0[2 * e], t0[2 * e + 1]} : f32x2{t1v[2 * e - 4], t1v[2 * e - 3]};
+          const f32x2 v2 = x2 * w2 + b2;
+          const unsigned v = HT::pk(v2[0], v2[1]);
+          pk[e] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
+        }
+        memcpy(&bfr[s2], pk, 16);
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int ot = 0; ot < 2; ++ot) {
+          const s16x8 af = *(const s16x8*)(a2l + (((k * 2 + ot) * 2 + mt) * 2 + s2) * 1024);
+          acc2[ot] = HT::mfma(af, bfr[s2], acc2[ot]);
+        }
+    };
+    s16x8 hf[2][2] = {};
+    f32x16 d1b[2];
+    hidden(0, hf[0]);
+    hidden(1, hf[1]);
+    d1b[0] = d1calc(0, 0, hf[0]);
+#pragma unroll
+    for (int st = 0; st < 18; ++st) {
+      const int k = st >> 1, mt = st & 1;
+      if (st + 1 < 18) {
+        const int k2 = (st + 1) >> 1, mt2 = (st + 1) & 1;
+        d1b[(st + 1) & 1] = d1calc(k2, mt2, hf[k2 & 1]);
+      }
+      elem(k, mt, d1b[st & 1]);
+      // buffer hf[k & 1] is free once d1calc(k, 1) has been issued, i.e. after step (k, 0): tap k + 2 goes in during step (k, 1)
+      if (mt == 1 && k + 2 < 9 && k + 2 != META_CENTRE_TAP) hidden(k + 2, hf[k & 1]);
     }
-    }
-    // epilogue: BN + ReLU, 16 contiguous output channels per (lane, ot)
+    // epilogue: BN + ReLU, 16 contiguous output channels per (lane, ot).  The ReLU comes after the 16-bit conversion, as a packed
+    // integer max (same bits: a negative value converts to a negative pattern)
     if (live) {
       bf16_t* yp = yout + (((size_t)b * a.H + h) * a.W + w) * a.y_cs + a.y_co;
 #pragma unroll
@@ -691,18 +586,49 @@ __global__ __launch_bounds__(WAVES * 64) void meta16_kernel(MetaArgs a) {
         unsigned pk[8];
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-          if constexpr (V & 64) {   // ReLU after the 16-bit conversion, as a packed integer max (same bits: a negative value converts to a negative pattern)
-            const unsigned v = HT::pk(acc2[ot][r] * cs2[ob + r] + cs2[64 + ob + r], acc2[ot][r + 1] * cs2[ob + r + 1] + cs2[64 + ob + r + 1]);
-            pk[r >> 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-          } else
-          pk[r >> 1] = HT::pk(fmaxf(acc2[ot][r] * cs2[ob + r] + cs2[64 + ob + r], 0.f),
-                                       fmaxf(acc2[ot][r + 1] * cs2[ob + r + 1] + cs2[64 + ob + r + 1], 0.f));
+          const unsigned v = HT::pk(acc2[ot][r] * cs2[ob + r] + cs2[64 + ob + r], acc2[ot][r + 1] * cs2[ob + r + 1] + cs2[64 + ob + r + 1]);
+          pk[r >> 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
         }
         *(Slot16*)(yp + ob) = Slot16{pk[0], pk[1], pk[2], pk[3]};
         *(Slot16*)(yp + ob + 8) = Slot16{pk[4], pk[5], pk[6], pk[7]};
       }
     }
   }
+}
+
+// ---- launch ----------------------------------------------------------------------------------------------------------
+// The caller (rd_meta_kernel_fwd) has checked pointers, dtype, shape and the channel strides / offsets.
+inline int launch_meta(const void* data, int d_cs, int d_co, const float* coord, const void* packed, void* y, int y_cs, int y_co,
+                       int B, int H, int W, int dt, hipStream_t st) {
+  MetaArgs a;
+  a.data = data; a.d_cs = d_cs; a.d_co = d_co; a.coord = coord; a.packed = (const unsigned char*)packed;
+  a.y = y; a.y_cs = y_cs; a.y_co = y_co; a.B = B; a.H = H; a.W = W;
+  a.tiles_h = (H + META_WAVES - 1) / META_WAVES;
+  a.tiles_w = (W + 31) / 32;
+  a.ntiles = B * a.tiles_h * a.tiles_w;
+  a.r0 = 0; a.m0 = a.m1 = a.m2 = 0;
+  const dim3 block(META_WAVES * 64);
+  ProfScope ps(RD_PROF_META, st);
+  if (is_h16(dt)) {
+    static std::atomic<unsigned long long> seen{0};
+    once_per_device(seen, [] { allow_big_lds(meta16_kernel<RD_BF16>); allow_big_lds(meta16_kernel<RD_F16>); });
+    const dim3 grid(std::min(a.ntiles, conv_num_cus()));
+    const int strips = a.tiles_w * B;
+    a.r0 = strips % 8 == 0 ? 8 : strips;   // (MetaArgs::r0: XCD-aware tile order; a permutation for any grid)
+    RD_REQUIRE((unsigned long long)a.ntiles * (unsigned)std::max(a.r0, std::max(a.tiles_h, a.tiles_w)) < (1ull << 32), RD_ESHAPE,
+               "meta_kernel: %d tiles exceed the range of the tile decode", a.ntiles);
+    a.m0 = meta_magic(a.r0); a.m1 = meta_magic(a.tiles_h); a.m2 = meta_magic(a.tiles_w);
+    // (meta16_kernel's fetch: per-image halo offsets are 32-bit, built from 24-bit multiplies)
+    RD_REQUIRE((long)H * W < (1l << 23) && (long)H * W * d_cs < (1l << 31) && W < (1 << 23) && d_cs < (1 << 23), RD_ESHAPE,
+               "meta_kernel: image of %d x %d pixels x %d channels exceeds the 32-bit halo offsets", H, W, d_cs);
+    if (dt == RD_F16) hipLaunchKernelGGL(meta16_kernel<RD_F16>, grid, block, Meta16Lds::TOTAL, st, a);
+    else hipLaunchKernelGGL(meta16_kernel<RD_BF16>, grid, block, Meta16Lds::TOTAL, st, a);
+  } else {
+    static std::atomic<unsigned long long> seen32{0};
+    once_per_device(seen32, [] { allow_big_lds(meta_kernel); });
+    hipLaunchKernelGGL(meta_kernel, dim3(std::min(a.ntiles, 512)), block, Meta32Lds::TOTAL, st, a);
+  }
+  return check_launch("meta_kernel");
 }
 
 }  // namespace rd

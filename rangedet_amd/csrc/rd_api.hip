@@ -614,39 +614,7 @@ int rd_meta_kernel_fwd(const void* data, int d_cstride, int d_coff, const float*
   RD_REQUIRE(d_cstride % ch == 0 && d_coff % ch == 0 && y_cstride % ch == 0 && y_coff % ch == 0, RD_ESHAPE,
              "meta_kernel: channel strides/offsets must be 16-byte multiples");
   RD_REQUIRE(d_coff + 64 <= d_cstride && y_coff + 64 <= y_cstride, RD_ESHAPE, "meta_kernel: needs 64 channels");
-  hipStream_t st = (hipStream_t)stream;
-  MetaArgs a;
-  a.data = data; a.d_cs = d_cstride; a.d_co = d_coff; a.coord = coord_nchw; a.packed = (const unsigned char*)packed;
-  a.y = y; a.y_cs = y_cstride; a.y_co = y_coff; a.B = B; a.H = H; a.W = W;
-  constexpr int WAVES = 8;
-  a.tiles_h = (H + WAVES - 1) / WAVES;
-  a.tiles_w = (W + 31) / 32;
-  a.ntiles = B * a.tiles_h * a.tiles_w;
-  a.r0 = 0; a.m0 = a.m1 = a.m2 = 0;
-  const size_t consts = 9 * 64 * 4 * 2 + 1024;
-  ProfScope ps(RD_PROF_META, st);
-  if (is_h16(dtype)) {
-    const size_t lds = meta_layout(dtype).wbytes + consts + (size_t)(WAVES + 2) * 34 * 128 + 4096;
-    static std::atomic<unsigned long long> seen{0};
-    once_per_device(seen, [] { allow_big_lds(meta16_kernel<WAVES, RD_BF16>); allow_big_lds(meta16_kernel<WAVES, RD_F16>); });
-    const dim3 mgrid(std::min(a.ntiles, conv_num_cus())), mblock(WAVES * 64);
-    const int strips = a.tiles_w * B;
-    a.r0 = strips % 8 == 0 ? 8 : strips;   // (MetaArgs::r0: XCD-aware tile order; a permutation for any grid)
-    RD_REQUIRE((unsigned long long)a.ntiles * (unsigned)std::max(a.r0, std::max(a.tiles_h, a.tiles_w)) < (1ull << 32), RD_ESHAPE,
-               "meta_kernel: %d tiles exceed the range of the tile decode", a.ntiles);
-    a.m0 = meta_magic(a.r0); a.m1 = meta_magic(a.tiles_h); a.m2 = meta_magic(a.tiles_w);
-    // (form 8 of the kernel: per-image halo offsets are 32-bit, built from 24-bit multiplies)
-    RD_REQUIRE((long)H * W < (1l << 23) && (long)H * W * d_cstride < (1l << 31) && W < (1 << 23) && d_cstride < (1 << 23), RD_ESHAPE,
-               "meta_kernel: image of %d x %d pixels x %d channels exceeds the 32-bit halo offsets", H, W, d_cstride);
-    if (dtype == RD_F16) hipLaunchKernelGGL((meta16_kernel<WAVES, RD_F16>), mgrid, mblock, lds, st, a);
-    else hipLaunchKernelGGL((meta16_kernel<WAVES, RD_BF16>), mgrid, mblock, lds, st, a);
-  } else {
-    const size_t lds = consts + (size_t)(WAVES + 2) * 34 * 256;
-    static std::atomic<unsigned long long> seen32{0};
-    once_per_device(seen32, [] { allow_big_lds(meta_kernel<RD_F32, WAVES>); });
-    hipLaunchKernelGGL((meta_kernel<RD_F32, WAVES>), dim3(std::min(a.ntiles, 512)), dim3(WAVES * 64), lds, st, a);
-  }
-  return check_launch("meta_kernel");
+  return launch_meta(data, d_cstride, d_coff, coord_nchw, packed, y, y_cstride, y_coff, B, H, W, dtype, (hipStream_t)stream);
 }
 
 // ---- post-processing -------------------------------------------------------------------------------------------

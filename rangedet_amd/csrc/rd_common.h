@@ -63,6 +63,18 @@ inline void once_per_device(std::atomic<unsigned long long>& seen, F f) {
   seen.fetch_or(bit, std::memory_order_release);
 }
 
+// Compute units of the current device: the grid of every persistent kernel (convs, fused block, Meta-Kernel) is a multiple of it.
+// -DRD_BUILD_NUM_CUS=n fixes it at build time (k_conv3.h, build options).
+inline int conv_num_cus() {
+#ifdef RD_BUILD_NUM_CUS
+  return RD_BUILD_NUM_CUS;
+#else
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+  return v;
+#endif
+}
+
 // ---- per-kind event profiling ------------------------------------------------------------------------
 struct Prof {
   bool on = false;

@@ -1,5 +1,5 @@
 """Meta-Kernel alone at the production shape (B frames of 64 x 2656, bf16): average launch time over `reps` launches, GB/s of
-compulsory traffic (262 B/px) and TFLOP/s.  RD_META_VARIANT selects the kernel form (rd_api.hip).
+compulsory traffic (262 B/px) and TFLOP/s.
     python tools/meta_bench.py [B] [reps]"""
 import os
 import sys
@@ -42,6 +42,5 @@ e1.record()
 torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / reps
 by = B * H * W * (128 * 2 + 12)
-print("meta variant %-5s B=%d: %.1f us per launch, %.0f GB/s (%.1f %% of 8 TB/s), %.0f TFLOP/s, checksum %.4f" % (
-    os.environ.get("RD_META_VARIANT", "dflt"), B, us, by / us / 1e3, by / us / 1e3 / 80, B * 19.29e9 / us / 1e6,
-    float(y.float().abs().mean())))
+print("meta B=%d: %.1f us per launch, %.0f GB/s (%.1f %% of 8 TB/s), %.0f TFLOP/s, checksum %.4f" % (
+    B, us, by / us / 1e3, by / us / 1e3 / 80, B * 19.29e9 / us / 1e6, float(y.float().abs().mean())))
