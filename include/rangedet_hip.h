@@ -32,6 +32,9 @@
  *                                                                                 operator_cxx/src_cxx/assigner.h:11-109
  *   rd_rpn_loss               get_iou_target + get_vfl_loss + get_normalize_reg_loss of one level, with the gradients MakeLoss sends
  *                             back                                                head/builder.py:156-196,268-422, head/loss.py:4-30
+ *   rd_relu_affine_bwd,       the backward of a head tower (3x3 conv + norm + ReLU layers, 1x1 output conv with bias): ReLU / scale
+ *   rd_conv3x3_bwd_weight,    backward, conv weight gradient in float32, output-conv backward
+ *   rd_head_out_bwd                                                               head/builder.py:221-255, tools/train.py:358-360
  *   rd_range_image_from_points  get_range_image + range_image_mask                datasets/create_range_image_in_kitti.py:107-137,178
  *
  * Conventions
@@ -503,6 +506,45 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
                 int n_gt, const float* mask, const float* reg_target, const float* reg_weight, const float* reg_norm_weight, int B, int H,
                 int Wl, const rd_loss_param_t* p_host, float* cls_loss, float* reg_loss, float* d_logit, float* d_delta,
                 float* iou_target, float* boxes10, float* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- backward of a head tower: conv weight gradient, output-conv backward, ReLU + norm-scale backward --------------------------------
+ * A tower is four  relu(s[c] * conv3x3(x, W) + t[c])  layers at 128 channels and a 1x1 output conv with bias (rangedet/symbol/head/
+ * builder.py:221-255: rpn_{cls,reg}_conv_{0..3}_lvl_*, rpn_cls_logit_lvl_* with 1 and rpn_reg_delta_lvl_* with 8 outputs); s, t the folded
+ * normalisation.  Weight gradients are float32, as the optimiser keeps them under multi_precision (tools/train.py:358-360); activations
+ * and their gradients are RD_BF16 or RD_F16, channels-last with a channel stride and offset like everywhere (both multiples of 8, the
+ * tensors 16-byte aligned).  For one layer with z = conv3x3(x, W), y = relu(s z + t) and g = dL/dy:
+ *   dz = g [y > 0] s[c]                                                  rd_relu_affine_bwd
+ *   dW[co,ci,dh+1,dw+1] = sum_{b,h,w} dz[b,h,w,co] x[b,h+dh,w+dw,ci]      rd_conv3x3_bwd_weight (x zero outside the image)
+ *   dx[b,h,w,ci] = sum_{co,dh,dw} dz[b,h-dh,w-dw,co] W[co,ci,dh+1,dw+1]   rd_conv3x3_bn_act_ex (RD_SCALE_FOLDED, no activation, zero shift) on the
+ *                                                                        weight with its channel axes swapped and its taps flipped
+ * and for the output conv out[b,p,o] = sum_c w[o,c] x[b,p,c] + bias[o] (rd_head_out): rd_head_out_bwd.
+ * Every reduction is split over workgroups whose partial sums go to the caller's workspace and are added in index order by a second
+ * launch: no atomics, two calls on the same inputs give the same bits, and the bits do not depend on the device's CU count.  All launches
+ * go on `stream`, nothing synchronises, the contents of ws on entry do not matter.  Every check precedes the first launch.
+ * Not here: training-mode normalisation (batch statistics), the gradients of s and t, the concat conv, strided and transposed convs.
+ *
+ * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
+ * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
+ * dz may be g. */
+int rd_relu_affine_bwd(const void* g, int g_cstride, int g_coff, const void* y, int y_cstride, int y_coff, const float* scale, void* dz,
+                       int dz_cstride, int dz_coff, int B, int H, int W, int C, int dtype, void* stream);
+/* dW (cout, cin, 3, 3) float32 of a stride-1, pad-1 conv with cin, cout in {64, 128} (else RD_ESHAPE), any B, H, W >= 1.  fp32
+ * accumulation on the matrix cores over the pixel axis.  split: the most partial sums per output element (= workgroups per tap column
+ * and 64 output channels); 0: the library's choice (512 workgroups in all).  The workspace holds split x 9 x cout x cin floats at most:
+ * size it with the same split.  RD_EWORKSPACE: ws_bytes below that. */
+size_t rd_conv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split);
+int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                          int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* Backward of rd_head_out.  d_out: float32 at d_out[b*out_batch_stride + (n_off + h*W + w)*nout + o], exactly as rd_head_out writes `out`
+ * -- so rd_rpn_loss's flat d_logit / d_delta buffers are read in place.  x: the output conv's input (the post-ReLU output of the last
+ * tower conv), w (nout, cin) float32.  nout 1..8, cin 64 or 128 (else RD_ESHAPE).
+ *   dx[b,p,c] = sum_o d_out[b,p,o] w[o,c]   in the activation type; with relu_mask != 0 times [x > 0], with scale != NULL times scale[c]
+ *               (float32, rounded once at the end): with both, dx is the dz of the last tower conv.  dx may be NULL.
+ *   dw[o,c] = sum_{b,p} d_out[b,p,o] x[b,p,c],  dbias[o] = sum_{b,p} d_out[b,p,o]   float32 */
+size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout);
+int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const void* x, int x_cstride, int x_coff, const float* w,
+                    int relu_mask, const float* scale, void* dx, int dx_cstride, int dx_coff, float* dw, float* dbias, int B, int H,
+                    int W, int cin, int nout, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

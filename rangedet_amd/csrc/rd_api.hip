@@ -11,6 +11,7 @@
 #include "k_misc.h"
 #include "k_riou.h"
 #include "k_loss.h"
+#include "k_convbwd.h"
 #include "k_sort.h"
 #include "k_wnms.h"
 
@@ -1094,6 +1095,100 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
   hipLaunchKernelGGL(loss_pixel_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, a);
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, a.part_cls, a.part_reg, npix, 0.0f, stats + 2);
   return check_launch("rpn_loss");
+}
+
+// ---- backward of the head towers (k_convbwd.h) ------------------------------------------------------------------------------
+static bool nhwc16_ok(int cs, int co, int C) { return cs > 0 && cs % 8 == 0 && co >= 0 && co % 8 == 0 && co + C <= cs; }
+int rd_relu_affine_bwd(const void* g, int g_cstride, int g_coff, const void* y, int y_cstride, int y_coff, const float* scale, void* dz,
+                       int dz_cstride, int dz_coff, int B, int H, int W, int C, int dtype, void* stream) {
+  RD_REQUIRE(g && dz, RD_EINVAL, "relu_affine_bwd: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "relu_affine_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 8 && C % 8 == 0, RD_ESHAPE, "relu_affine_bwd: B %d, H %d, W %d, C %d (a multiple of 8)", B, H, W, C);
+  RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, C) && nhwc16_ok(dz_cstride, dz_coff, C) && (!y || nhwc16_ok(y_cstride, y_coff, C)), RD_ESHAPE,
+             "relu_affine_bwd: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)g | (uintptr_t)y | (uintptr_t)dz) % 16 == 0, RD_EINVAL, "relu_affine_bwd: the tensors must be 16-byte aligned");
+  const long npix = (long)B * H * W, nthreads = npix * (C / 8);
+  RD_REQUIRE((nthreads + 255) / 256 <= 0x7fffffffL, RD_ESHAPE, "relu_affine_bwd: %ld pixels", npix);
+  const dim3 grid((unsigned)((nthreads + 255) / 256));
+  hipStream_t st = (hipStream_t)stream;
+#define RD_RAB(DT_) hipLaunchKernelGGL((relu_affine_bwd_kernel<DT_>), grid, dim3(256), 0, st, (const unsigned short*)g, g_cstride, g_coff, \
+                                       (const unsigned short*)y, y_cstride, y_coff, scale, (unsigned short*)dz, dz_cstride, dz_coff, npix, C)
+  if (dtype == RD_F16) RD_RAB(RD_F16); else RD_RAB(RD_BF16);
+#undef RD_RAB
+  return check_launch("relu_affine_bwd");
+}
+
+size_t rd_conv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split) {
+  return B >= 1 && H >= 1 && W >= 1 && split >= 0 && bw_weight_shape_ok(cin, cout) ? bw_weight_ws_bytes(B, H, W, cin, cout, split) : 0;
+}
+int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                          int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "conv3x3_bwd_weight: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "conv3x3_bwd_weight: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "conv3x3_bwd_weight: split %d (0: the library's choice)", split);
+  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1, RD_ESHAPE, "conv3x3_bwd_weight: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bw_weight_shape_ok(cin, cout), RD_ESHAPE, "conv3x3_bwd_weight: cin %d, cout %d (each 64 or 128; stride 1, pad 1)", cin, cout);
+  RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
+             "conv3x3_bwd_weight: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dz) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)dW) % 4 == 0, RD_EINVAL,
+             "conv3x3_bwd_weight: x and dz must be 16-byte aligned, dW and the workspace 4-byte aligned");
+  const size_t need = bw_weight_ws_bytes(B, H, W, cin, cout, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "conv3x3_bwd_weight: workspace %zu < %zu bytes", ws_bytes, need);
+  const long S = bw_split(B, H, W, cout, split);
+  RD_REQUIRE(S <= 0x7fffffffL, RD_ESHAPE, "conv3x3_bwd_weight: split %ld", S);
+  BwdWArgs a;
+  a.x = (const unsigned short*)x; a.dz = (const unsigned short*)dz;
+  a.x_cs = x_cstride; a.x_co = x_coff; a.dz_cs = dz_cstride; a.dz_co = dz_coff;
+  a.B = B; a.H = H; a.W = W; a.nwt = (W + BW_PT - 1) / BW_PT; a.nhs = (H + BW_RH - 1) / BW_RH;
+  a.nchunks = bw_chunks(B, H, W);
+  a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, 3, cout / BW_COB);
+#define RD_BWW(DT_, CI_, CO_) hipLaunchKernelGGL((conv3_bwd_weight_kernel<DT_, CI_, CO_>), grid, dim3(256), 0, st, a)
+#define RD_BWW_DT(DT_) do { if (cin == 128) { if (cout == 128) RD_BWW(DT_, 128, 128); else RD_BWW(DT_, 128, 64); } \
+                            else { if (cout == 128) RD_BWW(DT_, 64, 128); else RD_BWW(DT_, 64, 64); } } while (0)
+  if (dtype == RD_F16) RD_BWW_DT(RD_F16); else RD_BWW_DT(RD_BF16);
+#undef RD_BWW_DT
+#undef RD_BWW
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
+  return check_launch("conv3x3_bwd_weight");
+}
+
+size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout) {
+  return B >= 1 && H >= 1 && W >= 1 && (cin == 64 || cin == 128) && nout >= 1 && nout <= 8 ? hob_ws_bytes((long)B * H * W, cin) : 0;
+}
+int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const void* x, int x_cstride, int x_coff, const float* w,
+                    int relu_mask, const float* scale, void* dx, int dx_cstride, int dx_coff, float* dw, float* dbias, int B, int H,
+                    int W, int cin, int nout, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(d_out && x && w && dw && dbias && ws, RD_EINVAL, "head_out_bwd: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "head_out_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1, RD_ESHAPE, "head_out_bwd: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(cin == 64 || cin == 128, RD_ESHAPE, "head_out_bwd: cin %d (64 or 128)", cin);
+  RD_REQUIRE(nout >= 1 && nout <= 8, RD_ESHAPE, "head_out_bwd: nout %d (1..8)", nout);
+  const long HW = (long)H * W, total = (long)B * HW;
+  RD_REQUIRE(n_off >= 0 && out_batch_stride >= (n_off + HW) * nout, RD_ESHAPE, "head_out_bwd: batch stride %ld < (n_off %ld + %ld) * %d",
+             out_batch_stride, n_off, HW, nout);
+  RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && (!dx || nhwc16_ok(dx_cstride, dx_coff, cin)), RD_ESHAPE,
+             "head_out_bwd: channel strides and offsets are multiples of 8 with coff + cin <= cstride");
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dx) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)d_out | (uintptr_t)dw | (uintptr_t)dbias) % 4 == 0, RD_EINVAL,
+             "head_out_bwd: x and dx must be 16-byte aligned, the float buffers 4-byte aligned");
+  const size_t need = hob_ws_bytes(total, cin);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "head_out_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+  HobArgs a;
+  a.d_out = d_out; a.obs = out_batch_stride; a.n_off = n_off; a.HW = HW; a.total = total;
+  const int nb = hob_blocks(total);
+  a.per_block = (total + nb - 1) / nb;
+  a.x = (const unsigned short*)x; a.x_cs = x_cstride; a.x_co = x_coff;
+  a.w = w; a.scale = scale; a.relu_mask = relu_mask ? 1 : 0; a.nout = nout;
+  a.dx = (unsigned short*)dx; a.dx_cs = dx_cstride; a.dx_co = dx_coff;
+  a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+#define RD_HOB(DT_) do { if (cin == 128) hipLaunchKernelGGL((head_out_bwd_kernel<DT_, 128>), dim3(nb), dim3(256), 0, st, a); \
+                         else hipLaunchKernelGGL((head_out_bwd_kernel<DT_, 64>), dim3(nb), dim3(256), 0, st, a); } while (0)
+  if (dtype == RD_F16) RD_HOB(RD_F16); else RD_HOB(RD_BF16);
+#undef RD_HOB
+  hipLaunchKernelGGL(head_out_bwd_reduce_kernel, dim3((nout * cin + nout + 255) / 256), dim3(256), 0, st, (const float*)ws, nb, cin, nout, dw, dbias);
+  return check_launch("head_out_bwd");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------

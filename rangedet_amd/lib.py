@@ -134,6 +134,14 @@ SIGNATURES = {
     "rd_rpn_loss_workspace_bytes": (c_size_t, [c_int, c_long]),
     "rd_rpn_loss": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_int, c_int]
                     + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "rd_relu_affine_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_void_p]),
+    "rd_conv3x3_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rd_conv3x3_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_head_out_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rd_head_out_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rd_prof_enable": (c_int, [c_int]),
     "rd_prof_reset": (c_int, []),
     "rd_prof_get": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_long)]),

@@ -8,7 +8,7 @@ loss maps and into what MakeLoss sends back to the logits and the deltas; the de
     RpnLoss.update_metrics(metric_list, out)                  # the config's six ScalarLoss objects
 
 This is not a recorded training graph: get_config(True) and the builder's loss methods keep raising, and nothing here goes back through
-the towers.  One class, iou_type 'bev'.
+the towers (rangedet_amd.backward.HeadTowerBackward takes d_logit / d_delta from here).  One class, iou_type 'bev'.
 """
 import ctypes
 
