@@ -35,6 +35,9 @@
  *   rd_relu_affine_bwd,       the backward of a head tower (3x3 conv + norm + ReLU layers, 1x1 output conv with bias): ReLU / scale
  *   rd_conv3x3_bwd_weight,    backward, conv weight gradient in float32, output-conv backward
  *   rd_head_out_bwd                                                               head/builder.py:221-255, tools/train.py:358-360
+ *   rd_bn_stats, rd_bn_fold,  training-mode BatchNorm + ReLU of a head-tower layer (normalizer_factory(type="localbn")), forward and
+ *   rd_affine_relu,           backward                                            mxnext/complicate.py:26-45, mxnext/simple.py:502-508,
+ *   rd_bn_relu_bwd                                                                head/builder.py:212-240
  *   rd_range_image_from_points  get_range_image + range_image_mask                datasets/create_range_image_in_kitti.py:107-137,178
  *
  * Conventions
@@ -521,7 +524,8 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * Every reduction is split over workgroups whose partial sums go to the caller's workspace and are added in index order by a second
  * launch: no atomics, two calls on the same inputs give the same bits, and the bits do not depend on the device's CU count.  All launches
  * go on `stream`, nothing synchronises, the contents of ws on entry do not matter.  Every check precedes the first launch.
- * Not here: training-mode normalisation (batch statistics), the gradients of s and t, the concat conv, strided and transposed convs.
+ * Training-mode normalisation (batch statistics, the gradients of gamma and beta) is the next section.  Not here: the concat conv,
+ * strided and transposed convs.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -545,6 +549,51 @@ size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout);
 int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const void* x, int x_cstride, int x_coff, const float* w,
                     int relu_mask, const float* scale, void* dx, int dx_cstride, int dx_coff, float* dw, float* dbias, int B, int H,
                     int W, int cin, int nout, int dtype, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- training-mode batch norm of a head-tower layer, forward and backward ----------------------------------------------------------------
+ * The reference builds every tower layer with normalizer_factory(type="localbn") (mxnext/complicate.py:26-45): mx.sym.BatchNorm with
+ * fix_gamma=False, use_global_stats=False, momentum 0.9, eps 1e-5 + 1e-10, named <conv name>_bn (mxnext/simple.py:502-508,
+ * head/builder.py:212-240).  z = conv3x3(x, W) is the unscaled conv output in the activation type (rd_conv3x3_bn_act_ex with RD_SCALE_FOLDED,
+ * an unscaled weight image, zero shift, no activation); n = B H W; everything below is float32, and every fused multiply-add is an fmaf:
+ * an operation not written fmaf is rounded on its own.  The exact operation order is in rangedet_amd/csrc/k_norm.h.
+ *   forward    mean[c], var[c] (biased)                                          rd_bn_stats
+ *              rstd = 1 / sqrtf(var + eps), a = gamma rstd, b = fmaf(-mean, a, beta), moving statistics    rd_bn_fold
+ *              y = round(max(fmaf(z, a, b), 0))                                  rd_affine_relu
+ *   backward   gy = g [fmaf(z, a, b) > 0], zh = (z - mean) rstd, dbeta = sum gy, dgamma = sum gy zh,
+ *              dz = round(gamma rstd (gy - dbeta / n - zh dgamma / n))           rd_bn_relu_bwd
+ * dz then feeds rd_conv3x3_bwd_weight and the data gradient directly (no rd_relu_affine_bwd).
+ * Tensors are RD_BF16 / RD_F16 channels-last with a channel stride and offset (multiples of 8, 16-byte aligned).  C in {8, 16, 32, 64, 128,
+ * 256}, else RD_ESHAPE.  Every check precedes the first launch, nothing synchronises, the contents of ws on entry do not matter, there are
+ * no atomics: a reduction writes per-workgroup partial sums to ws and a second launch adds them as a tree of fixed shape.  split: the
+ * most partial sums per channel; 0: the library's choice (1024).  There are min(split or 1024, ceil(n / 64)) of them, a function of the shape
+ * and of split only -- never of the device -- and two calls give the same bytes.  Size the workspace with the same split.
+ *
+ * rd_bn_stats: one sweep over z.  Each workgroup shifts its sums by a pilot value, the mean of PL = 2048 / C of its pixels spread evenly over
+ * its run, and the final launch merges the (pilot, sum, sum of squares) triples about the first workgroup's mean; E[z^2] - E[z]^2 about
+ * zero is never formed.  A channel holding one small integer everywhere gives that integer as mean in every bit and var == 0. */
+size_t rd_bn_stats_workspace_bytes(int B, int H, int W, int C, int split);
+int rd_bn_stats(const void* z, int z_cstride, int z_coff, float* mean, float* var, int B, int H, int W, int C, int split, int dtype, void* ws,
+                size_t ws_bytes, void* stream);
+/* One launch on C-element float32 device vectors, no host round trip:
+ *   rstd = 1.0f / sqrtf(var + eps);  a = gamma * rstd;  b = fmaf(-mean, a, beta)
+ *   om = 1.0f - momentum;  moving_mean = fmaf(moving_mean, momentum, mean * om)
+ *   vu = unbiased ? var * ((float)n / (float)(n - 1)) : var;  moving_var = fmaf(moving_var, momentum, vu * om)
+ * moving_mean / moving_var are updated in place; either may be NULL (left alone).  unbiased != 0 needs n >= 2 (else RD_ESHAPE). */
+int rd_bn_fold(const float* mean, const float* var, const float* gamma, const float* beta, float eps, float momentum, long n, int unbiased,
+               float* rstd, float* a, float* b, float* moving_mean, float* moving_var, int C, void* stream);
+/* y = round(relu ? max(fmaf(z, a[c], b[c]), 0) : fmaf(z, a[c], b[c])): one fused multiply-add, one rounding.  y may be z. */
+int rd_affine_relu(const void* z, int z_cstride, int z_coff, const float* a, const float* b, int relu, void* y, int y_cstride, int y_coff,
+                   int B, int H, int W, int C, int dtype, void* stream);
+/* Three launches: partial sums, their fixed-order sum into dbeta / dgamma, the elementwise dz.  g = dL/dy; a, b, mean, rstd as rd_bn_fold
+ * left them.  The ReLU mask is recomputed as [fmaf(z, a, b) > 0] -- y is not read; this differs from a mask on the stored y only where a
+ * positive float32 value rounds to zero in the 16-bit type (RD_F16: below 2^-25).  relu == 0: no mask (a and b may then be NULL).
+ *   gy = mask ? g : 0;  zh = (z - mean) * rstd;  dbeta = sum gy;  dgamma = sum fmaf(gy, zh, .)
+ *   dz = round(gr * fmaf(-zh, c2, gy - c1))  with c1 = dbeta / (float)n, c2 = dgamma / (float)n, gr = gamma * rstd
+ * dz may be g. */
+size_t rd_bn_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split);
+int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const float* a, const float* b,
+                   const float* mean, const float* rstd, const float* gamma, int relu, void* dz, int dz_cstride, int dz_coff, float* dgamma,
+                   float* dbeta, int B, int H, int W, int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

@@ -14,8 +14,18 @@ For one layer with z = conv3x3(x, W), y = relu(s z + t) (s, t the folded normali
     dx = conv3x3(dz, W flipped)          conv3x3_data_grad: the persistent forward launch on the weight with its channel axes swapped and
                                          its taps flipped (that launch rounds the weight to the activation type)
 Everything runs on the allocator's current stream without a host synchronisation; buffers are reused between calls of the same shape,
-so a result is valid until the next such call.  Inference-mode normalisation only (no batch statistics, no gradients of s and t); the
-level-0 conv_0 (input: the un-materialised 64 + 8 channel concat) and strided / transposed convs are refused.
+so a result is valid until the next such call.  HeadTowerBackward is the tower with inference-mode normalisation (fixed folded s and t);
+the level-0 conv_0 (input: the un-materialised 64 + 8 channel concat) and strided / transposed convs are refused.
+
+HeadTowerTrain is the tower as the reference trains it (normalizer_factory(type="localbn"), mxnext/complicate.py:26-45: BatchNorm with the
+batch's own statistics after every conv).  With z = conv3x3(x, W) rounded to the activation type, n = B H W, float32 (csrc/k_norm.h):
+    mean, var = statistics of z over B, H, W                       batch_norm_stats (rd_bn_stats: one sweep, deterministic)
+    rstd = 1 / sqrt(var + eps), a = gamma rstd, b = beta - mean a   rd_bn_fold, which also updates the moving statistics on the device
+    y = relu(a z + b)                                               rd_affine_relu          -- the three: batch_norm_relu_forward
+    gy = g [a z + b > 0], zh = (z - mean) rstd
+    dbeta = sum gy, dgamma = sum gy zh
+    dz = gamma rstd (gy - dbeta / n - zh dgamma / n)                batch_norm_relu_backward (rd_bn_relu_bwd)
+and dz feeds the weight and data gradients above directly.
 """
 import numpy as np
 
@@ -127,6 +137,66 @@ class _Ops:
                _stream(A))
         return _view16(A, dx, (B, H, W, cin), self.dt), A.view_f32(dw, (nout, cin)), A.view_f32(db, (nout,))
 
+    # ---- training-mode batch norm (csrc/k_norm.h); every vector below is a device buffer of C float32 values ------------------------------
+    def conv_unscaled(self, x, packed, cin, cout, tag=0):
+        """z = conv3x3(x, W) rounded to the activation type: the persistent launch on an unscaled weight image, zero shift, no activation;
+        packed = (image, zero shift) as pack_unscaled makes them"""
+        A, L = self.A, self.L
+        B, H, W = _check16(x, "x")[:3]
+        out = self.buf(("z", tag), B * H * W * cout * 2)
+        L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), cin, 0, A.ptr(packed[0]), None, A.ptr(packed[1]), None, 0, 0, None, 0, 0, 0, None,
+               A.ptr(out), cout, 0, B, H, W, cin, cout, 1, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, cout), self.dt)
+
+    def pack_unscaled(self, w_oihw):
+        w = np.asarray(w_oihw, np.float32)
+        cout, cin = w.shape[:2]
+        return self.A.upload(self.L.pack_conv3x3_ex(w, 1, cin, fold_scale=None, dtype=self.dt)), self.A.upload(np.zeros(cout, np.float32))
+
+    def _norm_ws(self, entry, z, split):
+        B, H, W, C = _check16(z, "z")
+        nws = self.L.raw(entry)(B, H, W, C, split)
+        if not nws:
+            raise NotImplementedError("%s: %d channels (8, 16, 32, 64, 128 or 256) with split %d" % (entry[:-16], C, split))
+        return (B, H, W, C), self.buf(("norm_ws", 0), nws), nws
+
+    def bn_stats(self, z, split=0, tag=0):
+        """z (B, H, W, C) -> the buffers of mean and biased variance over B, H, W"""
+        A, L = self.A, self.L
+        (B, H, W, C), ws, nws = self._norm_ws("rd_bn_stats_workspace_bytes", z, split)
+        mean, var = self.buf(("bn_mean", tag), C * 4), self.buf(("bn_var", tag), C * 4)
+        L.call("rd_bn_stats", rdlib.ptr(z), C, 0, A.ptr(mean), A.ptr(var), B, H, W, C, split, self.dt, A.ptr(ws), nws, _stream(A))
+        return mean, var
+
+    def bn_fold(self, mean, var, gamma, beta, moving_mean, moving_var, n, C, eps, momentum, unbiased=True, tag=0):
+        """-> the buffers rstd, a, b; moving_mean / moving_var (buffers or None) are updated in place"""
+        A = self.A
+        rstd, a, b = (self.buf((k, tag), C * 4) for k in ("bn_rstd", "bn_a", "bn_b"))
+        self.L.call("rd_bn_fold", A.ptr(mean), A.ptr(var), A.ptr(gamma), A.ptr(beta), eps, momentum, n, 1 if unbiased else 0, A.ptr(rstd), A.ptr(a),
+                    A.ptr(b), None if moving_mean is None else A.ptr(moving_mean), None if moving_var is None else A.ptr(moving_var), C, _stream(A))
+        return rstd, a, b
+
+    def affine_relu(self, z, a, b, relu=True, tag=0):
+        A = self.A
+        B, H, W, C = _check16(z, "z")
+        out = self.buf(("bn_y", tag), B * H * W * C * 2)
+        self.L.call("rd_affine_relu", rdlib.ptr(z), C, 0, A.ptr(a), A.ptr(b), 1 if relu else 0, A.ptr(out), C, 0, B, H, W, C, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, C), self.dt)
+
+    def bn_relu_bwd(self, g, z, saved, gamma, relu=True, split=0, tag=0):
+        """g, z (B, H, W, C); saved: the dict of buffers a, b, mean, rstd the forward kept -> dz, dgamma (C,), dbeta (C,)"""
+        A, L = self.A, self.L
+        (B, H, W, C), ws, nws = self._norm_ws("rd_bn_relu_bwd_workspace_bytes", z, split)
+        if _check16(g, "g") != (B, H, W, C):
+            raise ValueError("bn_relu_bwd: g %r and z %r differ" % (tuple(g.shape), tuple(z.shape)))
+        dz, dg, db = self.buf(("bn_dz", tag), B * H * W * C * 2), self.buf(("bn_dgamma", tag), C * 4), self.buf(("bn_dbeta", tag), C * 4)
+        L.call("rd_bn_relu_bwd", rdlib.ptr(g), C, 0, rdlib.ptr(z), C, 0, A.ptr(saved["a"]), A.ptr(saved["b"]), A.ptr(saved["mean"]), A.ptr(saved["rstd"]),
+               A.ptr(gamma), 1 if relu else 0, A.ptr(dz), C, 0, A.ptr(dg), A.ptr(db), B, H, W, C, split, self.dt, A.ptr(ws), nws, _stream(A))
+        return _view16(A, dz, (B, H, W, C), self.dt), A.view_f32(dg, (C,)), A.view_f32(db, (C,))
+
+
+BN_EPS = 1e-5 + 1e-10      # mxnext/complicate.py:26-45 (normalizer_factory(type="localbn"))
+BN_MOMENTUM = 0.9
 
 _OPS = {}
 
@@ -157,6 +227,147 @@ def head_out_backward(d_out, x, w, n_off=0, out_batch_stride=None, scale=None, r
     w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(len(w), -1))
     sc = None if scale is None else o.A.upload(np.ascontiguousarray(scale, dtype=np.float32))
     return o.head_out_bwd(d_out, x, o.A.upload(w), w.shape[0], n_off, out_batch_stride, sc, relu_mask)
+
+
+def _vec(o, v, C, what):
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    if v.shape != (C,):
+        raise ValueError("%s: %d float32 values, got shape %r" % (what, C, v.shape))
+    return o.A.upload(v)
+
+
+def batch_norm_stats(z, split=0, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """(mean, var) of a (B, H, W, C) device tensor of the activation type over B, H, W: float32 device vectors, the variance biased"""
+    o = _ops(dtype, lib, alloc)
+    C = int(z.shape[3])
+    mean, var = o.bn_stats(z, split)
+    return o.A.view_f32(mean, (C,)), o.A.view_f32(var, (C,))
+
+
+def batch_norm_relu_forward(z, gamma, beta, moving_mean, moving_var, eps=BN_EPS, momentum=BN_MOMENTUM, unbiased=True, relu=True, split=0,
+                            dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """y = relu(gamma (z - mean) / sqrt(var + eps) + beta) with the batch's own statistics (mx.sym.BatchNorm, use_global_stats=False) ->
+    (y, saved).  gamma, beta and the moving statistics are float32 host vectors; saved holds the device buffers a, b, mean, var, rstd that
+    batch_norm_relu_backward needs, and float32 device views 'moving_mean' / 'moving_var' of the updated moving statistics
+    (moving = moving * momentum + batch * (1 - momentum)).
+    unbiased=True feeds the moving variance var * n / (n - 1).  That is what the GPU batch-norm implementations the reference runs on do
+    (cuDNN's running variance, and MXNet's own CUDA kernel, use the unbiased estimate; its CPU operator uses the biased one) -- read from
+    their sources, not pinned by a run of the reference.  The normalisation itself always uses the biased variance."""
+    o = _ops(dtype, lib, alloc)
+    B, H, W, C = _check16(z, "z")
+    gd, bd, mm, mv = (_vec(o, v, C, k) for v, k in ((gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_var, "moving_var")))
+    mean, var = o.bn_stats(z, split)
+    rstd, a, b = o.bn_fold(mean, var, gd, bd, mm, mv, B * H * W, C, eps, momentum, unbiased)
+    saved = dict(a=a, b=b, mean=mean, var=var, rstd=rstd, relu=relu, moving_mean=o.A.view_f32(mm, (C,)), moving_var=o.A.view_f32(mv, (C,)))
+    return o.affine_relu(z, a, b, relu), saved
+
+
+def batch_norm_relu_backward(g, z, saved, gamma, split=0, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """g = dL/dy, z and saved as batch_norm_relu_forward had them, gamma a float32 host vector -> (dz, dgamma, dbeta)"""
+    o = _ops(dtype, lib, alloc)
+    return o.bn_relu_bwd(g, z, saved, _vec(o, gamma, int(z.shape[3]), "gamma"), saved.get("relu", True), split)
+
+
+class HeadTowerTrain:
+    """One tower ('cls' or 'reg') of one pyramid level as the reference trains it: every layer is conv3x3 (no bias) + BatchNorm with the
+    batch's own statistics + ReLU (normalizer_factory(type="localbn"), the BatchNorm named <conv name>_bn), then the 1x1 output conv.
+      conv_weights                 (cout, cin, 3, 3) float32, input side first; index `first_conv` names the first of them
+      gammas, betas                the BatchNorm parameters of each layer (cout values each)
+      moving_means, moving_vars    its auxiliary states: copied to the device once, updated there by every forward()
+    forward(x) -> the float32 head output (B, H * W, nout): per layer the unscaled conv, rd_bn_stats, rd_bn_fold, rd_affine_relu, then
+    rd_head_out.  backward(d_out, n_off) -> (the gradient of the tower input, {reference parameter name: float32 gradient}): rd_head_out_bwd,
+    then per layer rd_bn_relu_bwd, rd_conv3x3_bwd_weight and the data gradient.  aux() -> {name: float32 device vector} of the moving
+    statistics.  Nothing synchronises with the host.  Keeps x and every activation in self.acts, every conv output in self.zs, and after
+    backward() each layer's dL/dy, dz and input gradient in self.gs, self.dzs, self.dxs (input side first)."""
+
+    def __init__(self, conv_weights, gammas, betas, moving_means, moving_vars, out_weight, out_bias, kind="cls", level=0, first_conv=0,
+                 eps=BN_EPS, momentum=BN_MOMENTUM, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        if kind not in ("cls", "reg"):
+            raise ValueError("kind: 'cls' or 'reg', got %r" % (kind,))
+        self.ops = o = _Ops(dtype, lib, alloc)
+        A = o.A
+        if not (len(conv_weights) == len(gammas) == len(betas) == len(moving_means) == len(moving_vars)) or not conv_weights:
+            raise ValueError("one gamma, beta, moving mean and moving variance per conv weight, at least one layer")
+        self.eps, self.momentum = float(eps), float(momentum)
+        self.names, self.layers = [], []
+        chans = None
+        for i, w in enumerate(conv_weights):
+            w = np.asarray(w, np.float32)
+            name = "rpn_%s_conv_%d_lvl_%d" % (kind, first_conv + i, level)
+            if w.ndim != 4 or w.shape[2:] != (3, 3):
+                raise NotImplementedError("%s: kernel %r -- 3x3, stride 1, pad 1 only (no strided or transposed conv)" % (name, w.shape[2:]))
+            cout, cin = w.shape[:2]
+            if cin not in (64, 128) or cout not in (64, 128):
+                why = " (the level-0 conv_0 reads the un-materialised concat of 64 + 8 channels: the concat conv has no backward here)" \
+                    if cin == 72 else ""
+                raise NotImplementedError("%s: %d -> %d channels; the backward kernels run 64 or 128 on either side%s" % (name, cin, cout, why))
+            if chans is not None and cin != chans:
+                raise ValueError("%s: %d input channels after a layer with %d outputs" % (name, cin, chans))
+            chans = cout
+            self.names.append(name)
+            self.layers.append(dict(cin=cin, cout=cout, fwd=o.pack_unscaled(w), bwd=o.pack_data_grad(w),
+                                    gamma=_vec(o, gammas[i], cout, name + "_bn_gamma"), beta=_vec(o, betas[i], cout, name + "_bn_beta"),
+                                    mmean=_vec(o, moving_means[i], cout, name + "_bn_moving_mean"),
+                                    mvar=_vec(o, moving_vars[i], cout, name + "_bn_moving_var")))
+        ow = np.asarray(out_weight, np.float32)
+        ow = np.ascontiguousarray(ow.reshape(ow.shape[0], -1))
+        ob = np.ascontiguousarray(out_bias, dtype=np.float32)
+        self.nout = int(ow.shape[0])
+        if ow.shape[1] != chans or ob.shape != (self.nout,):
+            raise ValueError("output conv: weight (nout, %d) and bias (nout), got %r and %r" % (chans, ow.shape, ob.shape))
+        if self.nout not in (1, 8):
+            raise NotImplementedError("output conv with %d outputs: rpn_cls_logit has 1, rpn_reg_delta 8" % self.nout)
+        out_name = "rpn_cls_logit_lvl_%d" % level if kind == "cls" else "rpn_reg_delta_lvl_%d" % level
+        self.out_names = (out_name + "_weight", out_name + "_bias")
+        self.out_w, self.out_b = A.upload(ow), A.upload(ob)
+        self.acts = self.zs = self.saved = None
+
+    def aux(self):
+        A, out = self.ops.A, {}
+        for name, ly in zip(self.names, self.layers):
+            out[name + "_bn_moving_mean"] = A.view_f32(ly["mmean"], (ly["cout"],))
+            out[name + "_bn_moving_var"] = A.view_f32(ly["mvar"], (ly["cout"],))
+        return out
+
+    def forward(self, x, unbiased=True):
+        o = self.ops
+        A, L = o.A, o.L
+        B, H, W, C = _check16(x, "x")
+        if C != self.layers[0]["cin"]:
+            raise ValueError("forward: %d input channels, the first conv takes %d" % (C, self.layers[0]["cin"]))
+        acts, zs, saved = [x], [], []
+        for i, ly in enumerate(self.layers):
+            z = o.conv_unscaled(acts[-1], ly["fwd"], ly["cin"], ly["cout"], tag=i)
+            mean, var = o.bn_stats(z, tag=i)
+            rstd, a, b = o.bn_fold(mean, var, ly["gamma"], ly["beta"], ly["mmean"], ly["mvar"], B * H * W, ly["cout"], self.eps, self.momentum,
+                                   unbiased, tag=i)
+            zs.append(z)
+            saved.append(dict(a=a, b=b, mean=mean, var=var, rstd=rstd))
+            acts.append(o.affine_relu(z, a, b, tag=i))
+        out = o.buf(("out", 0), B * H * W * self.nout * 4)
+        L.call("rd_head_out", rdlib.ptr(acts[-1]), self.layers[-1]["cout"], 0, A.ptr(self.out_w), A.ptr(self.out_b), A.ptr(out), H * W * self.nout, 0,
+               B, H, W, self.layers[-1]["cout"], self.nout, o.dt, _stream(A))
+        self.acts, self.zs, self.saved = acts, zs, saved
+        return A.view_f32(out, (B, H * W, self.nout))
+
+    def backward(self, d_out, n_off=0, out_batch_stride=None):
+        """d_out: the float32 gradient of the head output, the level at pixel offset n_off of each frame's run -- RpnLoss's flat d_logit
+        (B, N) / d_delta (B, N, 8) are read in place."""
+        if self.acts is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
+        o, acts, n = self.ops, self.acts, len(self.layers)
+        last = self.layers[-1]
+        g, dw, db = o.head_out_bwd(d_out, acts[n], self.out_w, self.nout, n_off, out_batch_stride)
+        grads = {self.out_names[0]: dw.reshape(self.nout, last["cout"], 1, 1), self.out_names[1]: db}
+        gs, dzs, dxs = [None] * n, [None] * n, [None] * n
+        for i in range(n - 1, -1, -1):
+            ly, name = self.layers[i], self.names[i]
+            gs[i] = g
+            dzs[i], grads[name + "_bn_gamma"], grads[name + "_bn_beta"] = o.bn_relu_bwd(g, self.zs[i], self.saved[i], ly["gamma"], tag=i)
+            grads[name + "_weight"] = o.weight_grad(acts[i], dzs[i], tag=i)
+            g = dxs[i] = o.data_grad(dzs[i], ly["bwd"], tag=i)
+        self.gs, self.dzs, self.dxs = gs, dzs, dxs
+        return g, grads
 
 
 class HeadTowerBackward:

@@ -12,6 +12,7 @@
 #include "k_riou.h"
 #include "k_loss.h"
 #include "k_convbwd.h"
+#include "k_norm.h"
 #include "k_sort.h"
 #include "k_wnms.h"
 
@@ -1189,6 +1190,102 @@ int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const
 #undef RD_HOB
   hipLaunchKernelGGL(head_out_bwd_reduce_kernel, dim3((nout * cin + nout + 255) / 256), dim3(256), 0, st, (const float*)ws, nb, cin, nout, dw, dbias);
   return check_launch("head_out_bwd");
+}
+
+// ---- training-mode batch norm of a head-tower layer (k_norm.h) ---------------------------------------------------------------
+static bool nm_shape_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1; }
+size_t rd_bn_stats_workspace_bytes(int B, int H, int W, int C, int split) {
+  return nm_shape_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 3 * C * sizeof(float) : 0;
+}
+int rd_bn_stats(const void* z, int z_cstride, int z_coff, float* mean, float* var, int B, int H, int W, int C, int split, int dtype, void* ws,
+                size_t ws_bytes, void* stream) {
+  RD_REQUIRE(z && mean && var && ws, RD_EINVAL, "bn_stats: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "bn_stats: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "bn_stats: split %d (0: the library's choice)", split);
+  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "bn_stats: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "bn_stats: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C), RD_ESHAPE, "bn_stats: channel stride and offset are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE((uintptr_t)z % 16 == 0 && ((uintptr_t)mean | (uintptr_t)var | (uintptr_t)ws) % 4 == 0, RD_EINVAL,
+             "bn_stats: z must be 16-byte aligned, the float buffers 4-byte aligned");
+  const size_t need = rd_bn_stats_workspace_bytes(B, H, W, C, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "bn_stats: workspace %zu < %zu bytes", ws_bytes, need);
+  NmStatsArgs a;
+  a.z = (const unsigned short*)z; a.cs = z_cstride; a.co = z_coff; a.C = C;
+  a.npix = (long)B * H * W; a.P = (int)nm_parts(a.npix, split); a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == RD_F16) hipLaunchKernelGGL((bn_stats_partial_kernel<RD_F16>), dim3(a.P), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((bn_stats_partial_kernel<RD_BF16>), dim3(a.P), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C / 8), dim3(256), 0, st, (const float*)ws, a.P, C, a.npix, mean, var);
+  return check_launch("bn_stats");
+}
+
+int rd_bn_fold(const float* mean, const float* var, const float* gamma, const float* beta, float eps, float momentum, long n, int unbiased,
+               float* rstd, float* a, float* b, float* moving_mean, float* moving_var, int C, void* stream) {
+  RD_REQUIRE(mean && var && gamma && beta && rstd && a && b, RD_EINVAL, "bn_fold: null pointer");
+  RD_REQUIRE(C >= 1 && n >= 1 && (!unbiased || n >= 2), RD_ESHAPE, "bn_fold: C %d, n %ld (at least 2 for the unbiased moving variance)", C, n);
+  RD_REQUIRE(((uintptr_t)mean | (uintptr_t)var | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)rstd | (uintptr_t)a | (uintptr_t)b |
+              (uintptr_t)moving_mean | (uintptr_t)moving_var) % 4 == 0, RD_EINVAL, "bn_fold: the float buffers must be 4-byte aligned");
+  NmFoldArgs f;
+  f.mean = mean; f.var = var; f.gamma = gamma; f.beta = beta; f.eps = eps; f.momentum = momentum;
+  f.nratio = unbiased ? (float)n / (float)(n - 1) : 0.f;
+  f.rstd = rstd; f.a = a; f.b = b; f.mmean = moving_mean; f.mvar = moving_var; f.C = C;
+  hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, f);
+  return check_launch("bn_fold");
+}
+
+int rd_affine_relu(const void* z, int z_cstride, int z_coff, const float* a, const float* b, int relu, void* y, int y_cstride, int y_coff,
+                   int B, int H, int W, int C, int dtype, void* stream) {
+  RD_REQUIRE(z && a && b && y, RD_EINVAL, "affine_relu: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "affine_relu: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "affine_relu: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "affine_relu: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(y_cstride, y_coff, C), RD_ESHAPE,
+             "affine_relu: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)z | (uintptr_t)y) % 16 == 0 && ((uintptr_t)a | (uintptr_t)b) % 4 == 0, RD_EINVAL,
+             "affine_relu: the tensors must be 16-byte aligned, a and b 4-byte aligned");
+  NmAffineArgs f;
+  f.z = (const unsigned short*)z; f.z_cs = z_cstride; f.z_co = z_coff; f.a = a; f.b = b; f.relu = relu ? 1 : 0;
+  f.y = (unsigned short*)y; f.y_cs = y_cstride; f.y_co = y_coff; f.C = C; f.npix = (long)B * H * W;
+  const long nb = nm_ew_blocks(f.npix, C);
+  RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "affine_relu: %ld pixels", f.npix);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == RD_F16) hipLaunchKernelGGL((affine_relu_kernel<RD_F16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((affine_relu_kernel<RD_BF16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  return check_launch("affine_relu");
+}
+
+size_t rd_bn_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split) {
+  return nm_shape_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 2 * C * sizeof(float) : 0;
+}
+int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const float* a, const float* b,
+                   const float* mean, const float* rstd, const float* gamma, int relu, void* dz, int dz_cstride, int dz_coff, float* dgamma,
+                   float* dbeta, int B, int H, int W, int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(g && z && mean && rstd && gamma && dz && dgamma && dbeta && ws && (!relu || (a && b)), RD_EINVAL, "bn_relu_bwd: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "bn_relu_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "bn_relu_bwd: split %d (0: the library's choice)", split);
+  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "bn_relu_bwd: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "bn_relu_bwd: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, C) && nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(dz_cstride, dz_coff, C), RD_ESHAPE,
+             "bn_relu_bwd: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)g | (uintptr_t)z | (uintptr_t)dz) % 16 == 0 &&
+             ((uintptr_t)a | (uintptr_t)b | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)ws) % 4 == 0,
+             RD_EINVAL, "bn_relu_bwd: the tensors must be 16-byte aligned, the float buffers 4-byte aligned");
+  const size_t need = rd_bn_relu_bwd_workspace_bytes(B, H, W, C, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "bn_relu_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+  NmBwdArgs f;
+  f.g = (const unsigned short*)g; f.z = (const unsigned short*)z; f.g_cs = g_cstride; f.g_co = g_coff; f.z_cs = z_cstride; f.z_co = z_coff;
+  f.a = a; f.b = b; f.mean = mean; f.rstd = rstd; f.gamma = gamma; f.relu = relu ? 1 : 0;
+  f.dz = (unsigned short*)dz; f.dz_cs = dz_cstride; f.dz_co = dz_coff; f.C = C;
+  f.npix = (long)B * H * W; f.P = (int)nm_parts(f.npix, split); f.part = (float*)ws; f.dgamma = dgamma; f.dbeta = dbeta;
+  const long nb = nm_ew_blocks(f.npix, C);
+  RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "bn_relu_bwd: %ld pixels", f.npix);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == RD_F16) hipLaunchKernelGGL((bn_bwd_partial_kernel<RD_F16>), dim3(f.P), dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((bn_bwd_partial_kernel<RD_BF16>), dim3(f.P), dim3(256), 0, st, f);
+  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 8, 2), dim3(256), 0, st, (const float*)ws, f.P, C, dbeta, dgamma);
+  if (dtype == RD_F16) hipLaunchKernelGGL((bn_bwd_dz_kernel<RD_F16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((bn_bwd_dz_kernel<RD_BF16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  return check_launch("bn_relu_bwd");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------

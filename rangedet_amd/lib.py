@@ -142,6 +142,15 @@ SIGNATURES = {
     "rd_head_out_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rd_head_out_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_bn_stats_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rd_bn_stats": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                            c_void_p]),
+    "rd_bn_fold": (c_int, [c_void_p] * 4 + [c_float, c_float, c_long, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
+    "rd_affine_relu": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_void_p]),
+    "rd_bn_relu_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rd_bn_relu_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_void_p,
+                               c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rd_prof_enable": (c_int, [c_int]),
     "rd_prof_reset": (c_int, []),
     "rd_prof_get": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_long)]),
