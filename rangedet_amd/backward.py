@@ -14,7 +14,10 @@ For one layer with z = conv3x3(x, W), y = relu(s z + t) (s, t the folded normali
     dx = conv3x3(dz, W flipped)          conv3x3_data_grad: the persistent forward launch on the weight with its channel axes swapped and
                                          its taps flipped (that launch rounds the weight to the activation type)
 Everything runs on the allocator's current stream without a host synchronisation; buffers are reused between calls of the same shape,
-so a result is valid until the next such call.  HeadTowerBackward is the tower with inference-mode normalisation (fixed folded s and t);
+so a result is valid until the next such call.  TowerOps holds the single steps, one method per library call (conv3x3 is the one forward
+conv launch: the towers' forward, the unscaled conv and the data gradient all go through it).  _HeadTower is the skeleton both towers
+share -- the layer checks, the parameter names, the output conv, the forward and backward loops; a tower adds its layer parameters, one
+layer's forward and the step from dL/dy to dz.  HeadTowerBackward is the tower with inference-mode normalisation (fixed folded s and t);
 the level-0 conv_0 (input: the un-materialised 64 + 8 channel concat) and strided / transposed convs are refused.
 
 HeadTowerTrain is the tower as the reference trains it (normalizer_factory(type="localbn"), mxnext/complicate.py:26-45: BatchNorm with the
@@ -58,7 +61,7 @@ def _check16(x, what):
     return tuple(int(v) for v in x.shape)
 
 
-class _Ops:
+class TowerOps:
     """The single steps on one (lib, allocator, dtype); buffers keyed by (step, shape, tag)."""
 
     def __init__(self, dtype=rdlib.RD_BF16, lib=None, alloc=None):
@@ -85,15 +88,19 @@ class _Ops:
         wf = np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1])
         return self.A.upload(self.L.pack_conv3x3_ex(wf, 1, cout, fold_scale=None, dtype=self.dt)), self.A.upload(np.zeros(cin, np.float32)), cin
 
+    def conv3x3(self, x, image, shift, cin, cout, flags, key):
+        """the persistent forward launch: x (B, H, W, cin) -> (B, H, W, cout) in the buffer `key`; image a packed weight, shift cout float32"""
+        A = self.A
+        B, H, W = _check16(x, "x")[:3]
+        out = self.buf(key, B * H * W * cout * 2)
+        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), cin, 0, A.ptr(image), None, A.ptr(shift), None, 0, 0, None, 0, 0, 0, None,
+                    A.ptr(out), cout, 0, B, H, W, cin, cout, 1, flags, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, cout), self.dt)
+
     def data_grad(self, dz, packed, tag=0):
         """dz (B, H, W, cout) -> dx (B, H, W, cin); packed = pack_data_grad(W)"""
-        A, L = self.A, self.L
         img, zero_shift, cin = packed
-        B, H, W, cout = _check16(dz, "dz")
-        out = self.buf(("dx", tag), B * H * W * cin * 2)
-        L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(dz), cout, 0, A.ptr(img), None, A.ptr(zero_shift), None, 0, 0, None, 0, 0, 0, None,
-               A.ptr(out), cin, 0, B, H, W, cout, cin, 1, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
-        return _view16(A, out, (B, H, W, cin), self.dt)
+        return self.conv3x3(dz, img, zero_shift, _check16(dz, "dz")[3], cin, rdlib.RD_SCALE_FOLDED, ("dx", tag))
 
     def weight_grad(self, x, dz, tag=0, split=0):
         """x (B, H, W, cin), dz (B, H, W, cout) -> dW (cout, cin, 3, 3) float32"""
@@ -141,12 +148,7 @@ class _Ops:
     def conv_unscaled(self, x, packed, cin, cout, tag=0):
         """z = conv3x3(x, W) rounded to the activation type: the persistent launch on an unscaled weight image, zero shift, no activation;
         packed = (image, zero shift) as pack_unscaled makes them"""
-        A, L = self.A, self.L
-        B, H, W = _check16(x, "x")[:3]
-        out = self.buf(("z", tag), B * H * W * cout * 2)
-        L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), cin, 0, A.ptr(packed[0]), None, A.ptr(packed[1]), None, 0, 0, None, 0, 0, 0, None,
-               A.ptr(out), cout, 0, B, H, W, cin, cout, 1, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
-        return _view16(A, out, (B, H, W, cout), self.dt)
+        return self.conv3x3(x, packed[0], packed[1], cin, cout, rdlib.RD_SCALE_FOLDED, ("z", tag))
 
     def pack_unscaled(self, w_oihw):
         w = np.asarray(w_oihw, np.float32)
@@ -203,15 +205,15 @@ _OPS = {}
 
 def _ops(dtype, lib, alloc):
     if lib is not None or alloc is not None:
-        return _Ops(dtype, lib, alloc)
+        return TowerOps(dtype, lib, alloc)
     if dtype not in _OPS:
-        _OPS[dtype] = _Ops(dtype)
+        _OPS[dtype] = TowerOps(dtype)
     return _OPS[dtype]
 
 
 def conv3x3_data_grad(dz, w_oihw, dtype=rdlib.RD_BF16, lib=None, alloc=None):
     """dL/dx of a stride-1, pad-1 3x3 conv: dz (B, H, W, cout) device tensor of the activation type, w the (cout, cin, 3, 3) float32 weight
-    on the host (packed on every call: keep a HeadTowerBackward, or _Ops.pack_data_grad, for repeated use)"""
+    on the host (packed on every call: keep a HeadTowerBackward, or TowerOps.pack_data_grad, for repeated use)"""
     o = _ops(dtype, lib, alloc)
     return o.data_grad(dz, o.pack_data_grad(w_oihw))
 
@@ -268,28 +270,18 @@ def batch_norm_relu_backward(g, z, saved, gamma, split=0, dtype=rdlib.RD_BF16, l
     return o.bn_relu_bwd(g, z, saved, _vec(o, gamma, int(z.shape[3]), "gamma"), saved.get("relu", True), split)
 
 
-class HeadTowerTrain:
-    """One tower ('cls' or 'reg') of one pyramid level as the reference trains it: every layer is conv3x3 (no bias) + BatchNorm with the
-    batch's own statistics + ReLU (normalizer_factory(type="localbn"), the BatchNorm named <conv name>_bn), then the 1x1 output conv.
-      conv_weights                 (cout, cin, 3, 3) float32, input side first; index `first_conv` names the first of them
-      gammas, betas                the BatchNorm parameters of each layer (cout values each)
-      moving_means, moving_vars    its auxiliary states: copied to the device once, updated there by every forward()
-    forward(x) -> the float32 head output (B, H * W, nout): per layer the unscaled conv, rd_bn_stats, rd_bn_fold, rd_affine_relu, then
-    rd_head_out.  backward(d_out, n_off) -> (the gradient of the tower input, {reference parameter name: float32 gradient}): rd_head_out_bwd,
-    then per layer rd_bn_relu_bwd, rd_conv3x3_bwd_weight and the data gradient.  aux() -> {name: float32 device vector} of the moving
-    statistics.  Nothing synchronises with the host.  Keeps x and every activation in self.acts, every conv output in self.zs, and after
-    backward() each layer's dL/dy, dz and input gradient in self.gs, self.dzs, self.dxs (input side first)."""
+class _HeadTower:
+    """What the two towers share: the layer checks and the reference's parameter names, the output conv, and the forward and backward
+    loops.  A subclass supplies _layer (one layer's device parameters), _layer_forward, _dz (dL/dy -> dz of a layer) and _out_bwd_kwargs.
+    `params`: one sequence per normalisation parameter, each with one entry per conv weight; `what` names them in the refusal."""
 
-    def __init__(self, conv_weights, gammas, betas, moving_means, moving_vars, out_weight, out_bias, kind="cls", level=0, first_conv=0,
-                 eps=BN_EPS, momentum=BN_MOMENTUM, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    def __init__(self, conv_weights, params, what, out_weight, out_bias, kind, level, first_conv, dtype, lib, alloc):
         if kind not in ("cls", "reg"):
             raise ValueError("kind: 'cls' or 'reg', got %r" % (kind,))
-        self.ops = o = _Ops(dtype, lib, alloc)
-        A = o.A
-        if not (len(conv_weights) == len(gammas) == len(betas) == len(moving_means) == len(moving_vars)) or not conv_weights:
-            raise ValueError("one gamma, beta, moving mean and moving variance per conv weight, at least one layer")
-        self.eps, self.momentum = float(eps), float(momentum)
-        self.names, self.layers = [], []
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        if any(len(p) != len(conv_weights) for p in params) or not conv_weights:
+            raise ValueError("one %s per conv weight, at least one layer" % what)
+        self._stems, self.layers = [], []
         chans = None
         for i, w in enumerate(conv_weights):
             w = np.asarray(w, np.float32)
@@ -304,11 +296,8 @@ class HeadTowerTrain:
             if chans is not None and cin != chans:
                 raise ValueError("%s: %d input channels after a layer with %d outputs" % (name, cin, chans))
             chans = cout
-            self.names.append(name)
-            self.layers.append(dict(cin=cin, cout=cout, fwd=o.pack_unscaled(w), bwd=o.pack_data_grad(w),
-                                    gamma=_vec(o, gammas[i], cout, name + "_bn_gamma"), beta=_vec(o, betas[i], cout, name + "_bn_beta"),
-                                    mmean=_vec(o, moving_means[i], cout, name + "_bn_moving_mean"),
-                                    mvar=_vec(o, moving_vars[i], cout, name + "_bn_moving_var")))
+            self._stems.append(name)
+            self.layers.append(dict(self._layer(w, name, *(p[i] for p in params)), cin=cin, cout=cout, bwd=o.pack_data_grad(w)))
         ow = np.asarray(out_weight, np.float32)
         ow = np.ascontiguousarray(ow.reshape(ow.shape[0], -1))
         ob = np.ascontiguousarray(out_bias, dtype=np.float32)
@@ -319,8 +308,67 @@ class HeadTowerTrain:
             raise NotImplementedError("output conv with %d outputs: rpn_cls_logit has 1, rpn_reg_delta 8" % self.nout)
         out_name = "rpn_cls_logit_lvl_%d" % level if kind == "cls" else "rpn_reg_delta_lvl_%d" % level
         self.out_names = (out_name + "_weight", out_name + "_bias")
-        self.out_w, self.out_b = A.upload(ow), A.upload(ob)
-        self.acts = self.zs = self.saved = None
+        self.out_w, self.out_b = o.A.upload(ow), o.A.upload(ob)
+        self.acts = None
+
+    def forward(self, x):
+        o = self.ops
+        A, last = o.A, self.layers[-1]
+        B, H, W, C = _check16(x, "x")
+        if C != self.layers[0]["cin"]:
+            raise ValueError("forward: %d input channels, the first conv takes %d" % (C, self.layers[0]["cin"]))
+        acts = [x]
+        for i in range(len(self.layers)):
+            acts.append(self._layer_forward(i, acts[-1]))
+        out = o.buf(("out", 0), B * H * W * self.nout * 4)
+        o.L.call("rd_head_out", rdlib.ptr(acts[-1]), last["cout"], 0, A.ptr(self.out_w), A.ptr(self.out_b), A.ptr(out), H * W * self.nout, 0,
+                 B, H, W, last["cout"], self.nout, o.dt, _stream(A))
+        self.acts = acts
+        return A.view_f32(out, (B, H * W, self.nout))
+
+    def backward(self, d_out, n_off=0, out_batch_stride=None):
+        """d_out: the float32 gradient of the head output, the level at pixel offset n_off of each frame's run -- RpnLoss's flat d_logit
+        (B, N) / d_delta (B, N, 8) are read in place.  -> (the gradient of the tower input in the activation type, {reference parameter
+        name: float32 gradient}).  Keeps each layer's dL/dy, dz and input gradient in self.gs, self.dzs, self.dxs (input side first)."""
+        if self.acts is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
+        o, acts, n = self.ops, self.acts, len(self.layers)
+        g, dw, db = o.head_out_bwd(d_out, acts[n], self.out_w, self.nout, n_off, out_batch_stride, **self._out_bwd_kwargs())
+        grads = {self.out_names[0]: dw.reshape(self.nout, self.layers[-1]["cout"], 1, 1), self.out_names[1]: db}
+        gs, dzs, dxs = [None] * n, [None] * n, [None] * n
+        for i in range(n - 1, -1, -1):
+            gs[i] = g
+            dzs[i] = self._dz(i, g, grads)
+            grads[self._stems[i] + "_weight"] = o.weight_grad(acts[i], dzs[i], tag=i)
+            g = dxs[i] = o.data_grad(dzs[i], self.layers[i]["bwd"], tag=i)
+        self.gs, self.dzs, self.dxs = gs, dzs, dxs
+        return g, grads
+
+
+class HeadTowerTrain(_HeadTower):
+    """One tower ('cls' or 'reg') of one pyramid level as the reference trains it: every layer is conv3x3 (no bias) + BatchNorm with the
+    batch's own statistics + ReLU (normalizer_factory(type="localbn"), the BatchNorm named <conv name>_bn), then the 1x1 output conv.
+      conv_weights                 (cout, cin, 3, 3) float32, input side first; index `first_conv` names the first of them
+      gammas, betas                the BatchNorm parameters of each layer (cout values each)
+      moving_means, moving_vars    its auxiliary states: copied to the device once, updated there by every forward()
+    forward(x) -> the float32 head output (B, H * W, nout): per layer the unscaled conv, rd_bn_stats, rd_bn_fold, rd_affine_relu, then
+    rd_head_out.  backward(d_out, n_off) -> (the gradient of the tower input, {reference parameter name: float32 gradient}): rd_head_out_bwd,
+    then per layer rd_bn_relu_bwd, rd_conv3x3_bwd_weight and the data gradient.  aux() -> {name: float32 device vector} of the moving
+    statistics.  Nothing synchronises with the host.  Keeps x and every activation in self.acts, every conv output in self.zs, and after
+    backward() each layer's dL/dy, dz and input gradient in self.gs, self.dzs, self.dxs (input side first)."""
+
+    def __init__(self, conv_weights, gammas, betas, moving_means, moving_vars, out_weight, out_bias, kind="cls", level=0, first_conv=0,
+                 eps=BN_EPS, momentum=BN_MOMENTUM, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        super().__init__(conv_weights, (gammas, betas, moving_means, moving_vars), "gamma, beta, moving mean and moving variance",
+                         out_weight, out_bias, kind, level, first_conv, dtype, lib, alloc)
+        self.names = self._stems
+        self.eps, self.momentum = float(eps), float(momentum)
+        self.zs = self.saved = None
+
+    def _layer(self, w, name, gamma, beta, mmean, mvar):
+        o, cout = self.ops, w.shape[0]
+        return dict(fwd=o.pack_unscaled(w), gamma=_vec(o, gamma, cout, name + "_bn_gamma"), beta=_vec(o, beta, cout, name + "_bn_beta"),
+                    mmean=_vec(o, mmean, cout, name + "_bn_moving_mean"), mvar=_vec(o, mvar, cout, name + "_bn_moving_var"))
 
     def aux(self):
         A, out = self.ops.A, {}
@@ -330,48 +378,30 @@ class HeadTowerTrain:
         return out
 
     def forward(self, x, unbiased=True):
-        o = self.ops
-        A, L = o.A, o.L
-        B, H, W, C = _check16(x, "x")
-        if C != self.layers[0]["cin"]:
-            raise ValueError("forward: %d input channels, the first conv takes %d" % (C, self.layers[0]["cin"]))
-        acts, zs, saved = [x], [], []
-        for i, ly in enumerate(self.layers):
-            z = o.conv_unscaled(acts[-1], ly["fwd"], ly["cin"], ly["cout"], tag=i)
-            mean, var = o.bn_stats(z, tag=i)
-            rstd, a, b = o.bn_fold(mean, var, ly["gamma"], ly["beta"], ly["mmean"], ly["mvar"], B * H * W, ly["cout"], self.eps, self.momentum,
-                                   unbiased, tag=i)
-            zs.append(z)
-            saved.append(dict(a=a, b=b, mean=mean, var=var, rstd=rstd))
-            acts.append(o.affine_relu(z, a, b, tag=i))
-        out = o.buf(("out", 0), B * H * W * self.nout * 4)
-        L.call("rd_head_out", rdlib.ptr(acts[-1]), self.layers[-1]["cout"], 0, A.ptr(self.out_w), A.ptr(self.out_b), A.ptr(out), H * W * self.nout, 0,
-               B, H, W, self.layers[-1]["cout"], self.nout, o.dt, _stream(A))
-        self.acts, self.zs, self.saved = acts, zs, saved
-        return A.view_f32(out, (B, H * W, self.nout))
+        self._unbiased, self.zs, self.saved = unbiased, [], []
+        return super().forward(x)
 
-    def backward(self, d_out, n_off=0, out_batch_stride=None):
-        """d_out: the float32 gradient of the head output, the level at pixel offset n_off of each frame's run -- RpnLoss's flat d_logit
-        (B, N) / d_delta (B, N, 8) are read in place."""
-        if self.acts is None:
-            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
-        o, acts, n = self.ops, self.acts, len(self.layers)
-        last = self.layers[-1]
-        g, dw, db = o.head_out_bwd(d_out, acts[n], self.out_w, self.nout, n_off, out_batch_stride)
-        grads = {self.out_names[0]: dw.reshape(self.nout, last["cout"], 1, 1), self.out_names[1]: db}
-        gs, dzs, dxs = [None] * n, [None] * n, [None] * n
-        for i in range(n - 1, -1, -1):
-            ly, name = self.layers[i], self.names[i]
-            gs[i] = g
-            dzs[i], grads[name + "_bn_gamma"], grads[name + "_bn_beta"] = o.bn_relu_bwd(g, self.zs[i], self.saved[i], ly["gamma"], tag=i)
-            grads[name + "_weight"] = o.weight_grad(acts[i], dzs[i], tag=i)
-            g = dxs[i] = o.data_grad(dzs[i], ly["bwd"], tag=i)
-        self.gs, self.dzs, self.dxs = gs, dzs, dxs
-        return g, grads
+    def _layer_forward(self, i, x):
+        o, ly = self.ops, self.layers[i]
+        z = o.conv_unscaled(x, ly["fwd"], ly["cin"], ly["cout"], tag=i)
+        mean, var = o.bn_stats(z, tag=i)
+        rstd, a, b = o.bn_fold(mean, var, ly["gamma"], ly["beta"], ly["mmean"], ly["mvar"], int(np.prod(z.shape[:3])), ly["cout"], self.eps,
+                               self.momentum, self._unbiased, tag=i)
+        self.zs.append(z)
+        self.saved.append(dict(a=a, b=b, mean=mean, var=var, rstd=rstd))
+        return o.affine_relu(z, a, b, tag=i)
+
+    def _out_bwd_kwargs(self):
+        return {}
+
+    def _dz(self, i, g, grads):
+        name = self.names[i]
+        dz, grads[name + "_bn_gamma"], grads[name + "_bn_beta"] = self.ops.bn_relu_bwd(g, self.zs[i], self.saved[i], self.layers[i]["gamma"], tag=i)
+        return dz
 
 
-class HeadTowerBackward:
-    """One tower ('cls' or 'reg') of one pyramid level.
+class HeadTowerBackward(_HeadTower):
+    """One tower ('cls' or 'reg') of one pyramid level with inference-mode normalisation.
       conv_weights   the tower's (cout, cin, 3, 3) float32 conv weights, input side first; index `first_conv` names the first of them
       scales, shifts the folded normalisation of each layer (cout values each)
       out_weight     (nout, cin[, 1, 1]) and out_bias (nout): rpn_cls_logit (nout 1) / rpn_reg_delta (nout 8)
@@ -381,81 +411,25 @@ class HeadTowerBackward:
 
     def __init__(self, conv_weights, scales, shifts, out_weight, out_bias, kind="cls", level=0, first_conv=0, dtype=rdlib.RD_BF16,
                  lib=None, alloc=None):
-        if kind not in ("cls", "reg"):
-            raise ValueError("kind: 'cls' or 'reg', got %r" % (kind,))
-        self.ops = o = _Ops(dtype, lib, alloc)
-        A, L = o.A, o.L
-        if not (len(conv_weights) == len(scales) == len(shifts)) or not conv_weights:
-            raise ValueError("one scale and one shift per conv weight, at least one layer")
-        self.names, self.layers = [], []
-        chans = None
-        for i, (w, s, t) in enumerate(zip(conv_weights, scales, shifts)):
-            w = np.asarray(w, np.float32)
-            name = "rpn_%s_conv_%d_lvl_%d" % (kind, first_conv + i, level)
-            if w.ndim != 4 or w.shape[2:] != (3, 3):
-                raise NotImplementedError("%s: kernel %r -- 3x3, stride 1, pad 1 only (no strided or transposed conv)" % (name, w.shape[2:]))
-            cout, cin = w.shape[:2]
-            if cin not in (64, 128) or cout not in (64, 128):
-                why = " (the level-0 conv_0 reads the un-materialised concat of 64 + 8 channels: the concat conv has no backward here)" \
-                    if cin == 72 else ""
-                raise NotImplementedError("%s: %d -> %d channels; the backward kernels run 64 or 128 on either side%s" % (name, cin, cout, why))
-            if chans is not None and cin != chans:
-                raise ValueError("%s: %d input channels after a layer with %d outputs" % (name, cin, chans))
-            chans = cout
-            s, t = np.ascontiguousarray(s, dtype=np.float32), np.ascontiguousarray(t, dtype=np.float32)
-            if s.shape != (cout,) or t.shape != (cout,):
-                raise ValueError("%s: scale / shift of %d values" % (name, cout))
-            self.names.append(name + "_weight")
-            self.layers.append(dict(cin=cin, cout=cout, fwd=A.upload(L.pack_conv3x3_ex(w, 1, cin, fold_scale=s, dtype=dtype)), shift=A.upload(t),
-                                    scale=A.upload(s), bwd=o.pack_data_grad(w)))
-        ow = np.asarray(out_weight, np.float32)
-        ow = np.ascontiguousarray(ow.reshape(ow.shape[0], -1))
-        ob = np.ascontiguousarray(out_bias, dtype=np.float32)
-        self.nout = int(ow.shape[0])
-        if ow.shape[1] != chans or ob.shape != (self.nout,):
-            raise ValueError("output conv: weight (nout, %d) and bias (nout), got %r and %r" % (chans, ow.shape, ob.shape))
-        if self.nout not in (1, 8):
-            raise NotImplementedError("output conv with %d outputs: rpn_cls_logit has 1, rpn_reg_delta 8" % self.nout)
-        out_name = "rpn_cls_logit_lvl_%d" % level if kind == "cls" else "rpn_reg_delta_lvl_%d" % level
-        self.out_names = (out_name + "_weight", out_name + "_bias")
-        self.out_w, self.out_b = A.upload(ow), A.upload(ob)
-        self.acts = None
+        super().__init__(conv_weights, (scales, shifts), "scale and one shift", out_weight, out_bias, kind, level, first_conv, dtype, lib, alloc)
+        self.names = [s + "_weight" for s in self._stems]
 
-    def forward(self, x):
-        o = self.ops
-        A, L = o.A, o.L
-        B, H, W, C = _check16(x, "x")
-        if C != self.layers[0]["cin"]:
-            raise ValueError("forward: %d input channels, the first conv takes %d" % (C, self.layers[0]["cin"]))
-        st, acts = _stream(A), [x]
-        for i, ly in enumerate(self.layers):
-            y = o.buf(("act", i), B * H * W * ly["cout"] * 2)
-            L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(acts[-1]), ly["cin"], 0, A.ptr(ly["fwd"]), None, A.ptr(ly["shift"]), None, 0, 0, None, 0, 0, 0,
-                   None, A.ptr(y), ly["cout"], 0, B, H, W, ly["cin"], ly["cout"], 1, rdlib.RD_SCALE_FOLDED | rdlib.RD_RELU_PRE, o.dt, st)
-            acts.append(_view16(A, y, (B, H, W, ly["cout"]), o.dt))
-        out = o.buf(("out", 0), B * H * W * self.nout * 4)
-        L.call("rd_head_out", rdlib.ptr(acts[-1]), self.layers[-1]["cout"], 0, A.ptr(self.out_w), A.ptr(self.out_b), A.ptr(out), H * W * self.nout, 0,
-               B, H, W, self.layers[-1]["cout"], self.nout, o.dt, st)
-        self.acts = acts
-        return A.view_f32(out, (B, H * W, self.nout))
+    def _layer(self, w, name, s, t):
+        o, (cout, cin) = self.ops, w.shape[:2]
+        s, t = np.ascontiguousarray(s, dtype=np.float32), np.ascontiguousarray(t, dtype=np.float32)
+        if s.shape != (cout,) or t.shape != (cout,):
+            raise ValueError("%s: scale / shift of %d values" % (name, cout))
+        return dict(fwd=o.A.upload(o.L.pack_conv3x3_ex(w, 1, cin, fold_scale=s, dtype=o.dt)), shift=o.A.upload(t), scale=o.A.upload(s))
 
-    def backward(self, d_out, n_off=0, out_batch_stride=None):
-        """d_out: the float32 gradient of the head output, the level at pixel offset n_off of each frame's run -- RpnLoss's flat d_logit
-        (B, N) / d_delta (B, N, 8) are read in place.  Also keeps every layer's dz and input gradient in self.dzs / self.dxs (input side first)."""
-        if self.acts is None:
-            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
-        o, acts, n = self.ops, self.acts, len(self.layers)
-        last = self.layers[-1]
-        dz, dw, db = o.head_out_bwd(d_out, acts[n], self.out_w, self.nout, n_off, out_batch_stride, scale=last["scale"], relu_mask=True)
-        grads = {self.out_names[0]: dw.reshape(self.nout, last["cout"], 1, 1), self.out_names[1]: db}
-        dzs, dxs = [None] * n, [None] * n
-        dx = None
-        for i in range(n - 1, -1, -1):
-            ly = self.layers[i]
-            dzs[i] = dz
-            grads[self.names[i]] = o.weight_grad(acts[i], dz, tag=i)
-            dx = dxs[i] = o.data_grad(dz, ly["bwd"], tag=i)
-            if i > 0:
-                dz = o.relu_affine_bwd(dx, acts[i], self.layers[i - 1]["scale"], tag=i - 1)
-        self.dzs, self.dxs = dzs, dxs
-        return dx, grads
+    def _layer_forward(self, i, x):
+        ly = self.layers[i]
+        return self.ops.conv3x3(x, ly["fwd"], ly["shift"], ly["cin"], ly["cout"], rdlib.RD_SCALE_FOLDED | rdlib.RD_RELU_PRE, ("act", i))
+
+    def _out_bwd_kwargs(self):
+        """the output conv's backward applies the last layer's mask and scale itself: its dx is that layer's dz"""
+        return dict(scale=self.layers[-1]["scale"], relu_mask=True)
+
+    def _dz(self, i, g, grads):
+        if i == len(self.layers) - 1:
+            return g
+        return self.ops.relu_affine_bwd(g, self.acts[i + 1], self.layers[i]["scale"], tag=i)

@@ -181,20 +181,21 @@ __global__ __launch_bounds__(256) void relu_affine_bwd_kernel(const unsigned sho
   const Slot16 gv = *(const Slot16*)(g + p * g_cs + g_co + c);
   Slot16 yv = {0u, 0u, 0u, 0u};
   if (y) yv = *(const Slot16*)(y + p * y_cs + y_co + c);
-  Slot16 o;
+  float gf[8], yf[8];
+  slot_unpack<DT>(gv, gf);
+  slot_unpack<DT>(yv, yf);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2_t_ gf = H16<DT>::unpk(gv[k]), yf = H16<DT>::unpk(yv[k]);
-    const float s0 = scale ? scale[c + 2 * k] : 1.f, s1 = scale ? scale[c + 2 * k + 1] : 1.f;
-    const float r0 = (!y || yf[0] > 0.f) ? gf[0] * s0 : 0.f, r1 = (!y || yf[1] > 0.f) ? gf[1] * s1 : 0.f;
-    o[k] = H16<DT>::pk(r0, r1);
+  for (int j = 0; j < 8; ++j) {
+    const float s = scale ? scale[c + j] : 1.f;
+    gf[j] = (!y || yf[j] > 0.f) ? gf[j] * s : 0.f;
   }
-  *(Slot16*)(dz + p * dz_cs + dz_co + c) = o;
+  *(Slot16*)(dz + p * dz_cs + dz_co + c) = slot_pack<DT>(gf);
 }
 
 // ---- backward of the 1x1 output conv (rd_head_out) ----------------------------------------------------------------------------------------
 constexpr int HOB_MAX_BLOCKS = 1024;
 constexpr int HOB_MIN_PIXELS = 64;     // pixels of a block before a second block is worth its workspace slot
+// (kept apart from k_norm.h's nm_parts, like the final-reduce kernels: they split and add in different orders, merging would change result bits)
 inline int hob_blocks(long total) {
   const long nb = (total + HOB_MIN_PIXELS - 1) / HOB_MIN_PIXELS;
   return (int)(nb < 1 ? 1 : nb > HOB_MAX_BLOCKS ? HOB_MAX_BLOCKS : nb);
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(256) void head_out_bwd_kernel(HobArgs a) {
     const Slot16 xv = *(const Slot16*)(a.x + g * a.x_cs + a.x_co + cg * 8);
     float xf[8], r[8];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 4; ++k) {      // (not slot_unpack: through it the bf16 form compiles to a longer loop, measured 0.8 % slower)
       const f32x2_t_ t = H16<DT>::unpk(xv[k]);
       xf[2 * k] = t[0];
       xf[2 * k + 1] = t[1];
@@ -281,15 +282,8 @@ __global__ __launch_bounds__(256) void head_out_bwd_kernel(HobArgs a) {
       for (int j = 0; j < 8; ++j) red[pl][cg * 8 + j] = acc[o][j];
       if (cg == 0) redb[pl] = accb[o];
       __syncthreads();
-      if (tid < CIN) {
-        float sum = red[0][tid];
-        for (int q = 1; q < PL; ++q) sum += red[q][tid];
-        slot[o * CIN + tid] = sum;
-      } else if (tid == CIN) {
-        float sum = redb[0];
-        for (int q = 1; q < PL; ++q) sum += redb[q];
-        slot[8 * CIN + o] = sum;
-      }
+      if (tid < CIN) slot[o * CIN + tid] = lane_sum(&red[0][0], PL, CIN, tid);
+      else if (tid == CIN) slot[8 * CIN + o] = lane_sum(redb, PL, 1, 0);
       __syncthreads();
     }
 }

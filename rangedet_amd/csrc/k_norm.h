@@ -64,22 +64,6 @@ inline long nm_ew_blocks(long npix, int C) {
   return (npix + per - 1) / per;
 }
 
-template <int DT>
-__device__ __forceinline__ void nm_unpack(const Slot16 v, float (&f)[8]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2_t_ t = H16<DT>::unpk(v[k]);
-    f[2 * k] = t[0];
-    f[2 * k + 1] = t[1];
-  }
-}
-template <int DT>
-__device__ __forceinline__ Slot16 nm_pack(const float (&f)[8]) {
-  Slot16 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = H16<DT>::pk(f[2 * k], f[2 * k + 1]);
-  return o;
-}
 // NM_UNROLL pixels q0, q0 + PL, ... of one slot; an address at or past `hi` reads pixel hi - 1 (the caller drops the value)
 __device__ __forceinline__ void nm_load(const unsigned short* __restrict__ base, int cs, long q0, int PL, long hi, Slot16 (&v)[NM_UNROLL]) {
 #pragma unroll
@@ -87,13 +71,6 @@ __device__ __forceinline__ void nm_load(const unsigned short* __restrict__ base,
     const long q = q0 + (long)u * PL, qc = q < hi ? q : hi - 1;
     v[u] = *(const Slot16*)(base + qc * cs);
   }
-}
-// the PL lane values of channel `tid` (tid < C) added in lane order
-__device__ __forceinline__ float nm_lanes(const float* red, int PL, int C, int tid) {
-  _Pragma("clang fp contract(off)")
-  float s = red[tid];
-  for (int q = 1; q < PL; ++q) s += red[q * C + tid];
-  return s;
 }
 // one value per (kl, cl) -> the sum over kl of channel cl, the same in all 32 threads of the channel; every thread of the block calls it
 __device__ __forceinline__ float nm_tree32(float v, float (*red)[8], int kl, int cl) {
@@ -126,11 +103,11 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(NmStatsArgs a) {
   const long k = blockIdx.x, lo = k * a.npix / a.P, hi = (k + 1) * a.npix / a.P, nk = hi - lo;
   const unsigned short* zb = a.z + a.co + 8 * sl;
   float f[8];
-  nm_unpack<DT>(*(const Slot16*)(zb + (lo + (long)pl * nk / PL) * a.cs), f);
+  slot_unpack<DT>(*(const Slot16*)(zb + (lo + (long)pl * nk / PL) * a.cs), f);
 #pragma unroll
   for (int j = 0; j < 8; ++j) red[0][pl * C + 8 * sl + j] = f[j];
   __syncthreads();
-  if (tid < C) pil[tid] = nm_lanes(red[0], PL, C, tid) * (1.0f / PL);
+  if (tid < C) pil[tid] = lane_sum(red[0], PL, C, tid) * (1.0f / PL);
   __syncthreads();
   float p[8], s1[8], s2[8];
 #pragma unroll
@@ -145,7 +122,7 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(NmStatsArgs a) {
 #pragma unroll
     for (int u = 0; u < NM_UNROLL; ++u) {
       const bool ok = q0 + (long)u * PL < hi;
-      nm_unpack<DT>(v[u], f);
+      slot_unpack<DT>(v[u], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float d = ok ? f[j] - p[j] : 0.f;
@@ -162,8 +139,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(NmStatsArgs a) {
   __syncthreads();
   if (tid < C) {
     a.part[k * C + tid] = pil[tid];
-    a.part[((long)a.P + k) * C + tid] = nm_lanes(red[0], PL, C, tid);
-    a.part[(2L * a.P + k) * C + tid] = nm_lanes(red[1], PL, C, tid);
+    a.part[((long)a.P + k) * C + tid] = lane_sum(red[0], PL, C, tid);
+    a.part[(2L * a.P + k) * C + tid] = lane_sum(red[1], PL, C, tid);
   }
 }
 
@@ -253,13 +230,13 @@ __global__ __launch_bounds__(256) void affine_relu_kernel(NmAffineArgs a) {
     for (int u = 0; u < NM_UNROLL; ++u) {
       const long q = q0 + (long)u * PL;
       float f[8];
-      nm_unpack<DT>(v[u], f);
+      slot_unpack<DT>(v[u], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float t = fmaf(f[j], sa[j], sb[j]);
         f[j] = a.relu ? fmaxf(t, 0.f) : t;
       }
-      if (q < hi) *(Slot16*)(yb + q * a.y_cs) = nm_pack<DT>(f);
+      if (q < hi) *(Slot16*)(yb + q * a.y_cs) = slot_pack<DT>(f);
     }
   }
 }
@@ -303,8 +280,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(NmBwdArgs a) {
     for (int u = 0; u < NM_UNROLL; ++u) {
       const bool ok = q0 + (long)u * PL < hi;
       float fg[8], fz[8];
-      nm_unpack<DT>(vg[u], fg);
-      nm_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vg[u], fg);
+      slot_unpack<DT>(vz[u], fz);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool on = ok && (!a.relu || fmaf(fz[j], sa[j], sb[j]) > 0.f);
@@ -322,8 +299,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(NmBwdArgs a) {
   }
   __syncthreads();
   if (tid < C) {
-    a.part[k * C + tid] = nm_lanes(red[0], PL, C, tid);
-    a.part[((long)a.P + k) * C + tid] = nm_lanes(red[1], PL, C, tid);
+    a.part[k * C + tid] = lane_sum(red[0], PL, C, tid);
+    a.part[((long)a.P + k) * C + tid] = lane_sum(red[1], PL, C, tid);
   }
 }
 
@@ -369,8 +346,8 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(NmBwdArgs a) {
     for (int u = 0; u < NM_UNROLL; ++u) {
       const long q = q0 + (long)u * PL;
       float fg[8], fz[8];
-      nm_unpack<DT>(vg[u], fg);
-      nm_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vg[u], fg);
+      slot_unpack<DT>(vz[u], fz);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool on = !a.relu || fmaf(fz[j], sa[j], sb[j]) > 0.f;
@@ -378,7 +355,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(NmBwdArgs a) {
         const float zh = (fz[j] - mu[j]) * rs[j];
         fg[j] = gr[j] * fmaf(-zh, c2[j], gy - c1[j]);
       }
-      if (q < hi) *(Slot16*)(ob + q * a.dz_cs) = nm_pack<DT>(fg);
+      if (q < hi) *(Slot16*)(ob + q * a.dz_cs) = slot_pack<DT>(fg);
     }
   }
 }

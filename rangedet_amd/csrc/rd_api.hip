@@ -1100,11 +1100,12 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
 
 // ---- backward of the head towers (k_convbwd.h) ------------------------------------------------------------------------------
 static bool nhwc16_ok(int cs, int co, int C) { return cs > 0 && cs % 8 == 0 && co >= 0 && co % 8 == 0 && co + C <= cs; }
+static bool bhw_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1; }
 int rd_relu_affine_bwd(const void* g, int g_cstride, int g_coff, const void* y, int y_cstride, int y_coff, const float* scale, void* dz,
                        int dz_cstride, int dz_coff, int B, int H, int W, int C, int dtype, void* stream) {
   RD_REQUIRE(g && dz, RD_EINVAL, "relu_affine_bwd: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "relu_affine_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
-  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 8 && C % 8 == 0, RD_ESHAPE, "relu_affine_bwd: B %d, H %d, W %d, C %d (a multiple of 8)", B, H, W, C);
+  RD_REQUIRE(bhw_ok(B, H, W) && C >= 8 && C % 8 == 0, RD_ESHAPE, "relu_affine_bwd: B %d, H %d, W %d, C %d (a multiple of 8)", B, H, W, C);
   RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, C) && nhwc16_ok(dz_cstride, dz_coff, C) && (!y || nhwc16_ok(y_cstride, y_coff, C)), RD_ESHAPE,
              "relu_affine_bwd: channel strides and offsets are multiples of 8 with coff + C <= cstride");
   RD_REQUIRE(((uintptr_t)g | (uintptr_t)y | (uintptr_t)dz) % 16 == 0, RD_EINVAL, "relu_affine_bwd: the tensors must be 16-byte aligned");
@@ -1112,22 +1113,20 @@ int rd_relu_affine_bwd(const void* g, int g_cstride, int g_coff, const void* y, 
   RD_REQUIRE((nthreads + 255) / 256 <= 0x7fffffffL, RD_ESHAPE, "relu_affine_bwd: %ld pixels", npix);
   const dim3 grid((unsigned)((nthreads + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
-#define RD_RAB(DT_) hipLaunchKernelGGL((relu_affine_bwd_kernel<DT_>), grid, dim3(256), 0, st, (const unsigned short*)g, g_cstride, g_coff, \
-                                       (const unsigned short*)y, y_cstride, y_coff, scale, (unsigned short*)dz, dz_cstride, dz_coff, npix, C)
-  if (dtype == RD_F16) RD_RAB(RD_F16); else RD_RAB(RD_BF16);
-#undef RD_RAB
+  RD_LAUNCH_H16(dtype, (relu_affine_bwd_kernel<DT>), grid, dim3(256), st, (const unsigned short*)g, g_cstride, g_coff, (const unsigned short*)y,
+                y_cstride, y_coff, scale, (unsigned short*)dz, dz_cstride, dz_coff, npix, C);
   return check_launch("relu_affine_bwd");
 }
 
 size_t rd_conv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split) {
-  return B >= 1 && H >= 1 && W >= 1 && split >= 0 && bw_weight_shape_ok(cin, cout) ? bw_weight_ws_bytes(B, H, W, cin, cout, split) : 0;
+  return bhw_ok(B, H, W) && split >= 0 && bw_weight_shape_ok(cin, cout) ? bw_weight_ws_bytes(B, H, W, cin, cout, split) : 0;
 }
 int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
                           int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
   RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "conv3x3_bwd_weight: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "conv3x3_bwd_weight: dtype %d (RD_BF16 or RD_F16)", dtype);
   RD_REQUIRE(split >= 0, RD_EINVAL, "conv3x3_bwd_weight: split %d (0: the library's choice)", split);
-  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1, RD_ESHAPE, "conv3x3_bwd_weight: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "conv3x3_bwd_weight: B %d, H %d, W %d", B, H, W);
   RD_REQUIRE(bw_weight_shape_ok(cin, cout), RD_ESHAPE, "conv3x3_bwd_weight: cin %d, cout %d (each 64 or 128; stride 1, pad 1)", cin, cout);
   RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
              "conv3x3_bwd_weight: channel strides and offsets are multiples of 8 with coff + C <= cstride");
@@ -1145,25 +1144,23 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   a.part = (float*)ws;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)S, 3, cout / BW_COB);
-#define RD_BWW(DT_, CI_, CO_) hipLaunchKernelGGL((conv3_bwd_weight_kernel<DT_, CI_, CO_>), grid, dim3(256), 0, st, a)
-#define RD_BWW_DT(DT_) do { if (cin == 128) { if (cout == 128) RD_BWW(DT_, 128, 128); else RD_BWW(DT_, 128, 64); } \
-                            else { if (cout == 128) RD_BWW(DT_, 64, 128); else RD_BWW(DT_, 64, 64); } } while (0)
-  if (dtype == RD_F16) RD_BWW_DT(RD_F16); else RD_BWW_DT(RD_BF16);
-#undef RD_BWW_DT
-#undef RD_BWW
+  if (cin == 128 && cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 128>), grid, dim3(256), st, a);
+  else if (cin == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 64>), grid, dim3(256), st, a);
+  else if (cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
   hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
   return check_launch("conv3x3_bwd_weight");
 }
 
 size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout) {
-  return B >= 1 && H >= 1 && W >= 1 && (cin == 64 || cin == 128) && nout >= 1 && nout <= 8 ? hob_ws_bytes((long)B * H * W, cin) : 0;
+  return bhw_ok(B, H, W) && (cin == 64 || cin == 128) && nout >= 1 && nout <= 8 ? hob_ws_bytes((long)B * H * W, cin) : 0;
 }
 int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const void* x, int x_cstride, int x_coff, const float* w,
                     int relu_mask, const float* scale, void* dx, int dx_cstride, int dx_coff, float* dw, float* dbias, int B, int H,
                     int W, int cin, int nout, int dtype, void* ws, size_t ws_bytes, void* stream) {
   RD_REQUIRE(d_out && x && w && dw && dbias && ws, RD_EINVAL, "head_out_bwd: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "head_out_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
-  RD_REQUIRE(B >= 1 && H >= 1 && W >= 1, RD_ESHAPE, "head_out_bwd: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "head_out_bwd: B %d, H %d, W %d", B, H, W);
   RD_REQUIRE(cin == 64 || cin == 128, RD_ESHAPE, "head_out_bwd: cin %d (64 or 128)", cin);
   RD_REQUIRE(nout >= 1 && nout <= 8, RD_ESHAPE, "head_out_bwd: nout %d (1..8)", nout);
   const long HW = (long)H * W, total = (long)B * HW;
@@ -1184,25 +1181,22 @@ int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const
   a.dx = (unsigned short*)dx; a.dx_cs = dx_cstride; a.dx_co = dx_coff;
   a.part = (float*)ws;
   hipStream_t st = (hipStream_t)stream;
-#define RD_HOB(DT_) do { if (cin == 128) hipLaunchKernelGGL((head_out_bwd_kernel<DT_, 128>), dim3(nb), dim3(256), 0, st, a); \
-                         else hipLaunchKernelGGL((head_out_bwd_kernel<DT_, 64>), dim3(nb), dim3(256), 0, st, a); } while (0)
-  if (dtype == RD_F16) RD_HOB(RD_F16); else RD_HOB(RD_BF16);
-#undef RD_HOB
+  if (cin == 128) RD_LAUNCH_H16(dtype, (head_out_bwd_kernel<DT, 128>), dim3(nb), dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (head_out_bwd_kernel<DT, 64>), dim3(nb), dim3(256), st, a);
   hipLaunchKernelGGL(head_out_bwd_reduce_kernel, dim3((nout * cin + nout + 255) / 256), dim3(256), 0, st, (const float*)ws, nb, cin, nout, dw, dbias);
   return check_launch("head_out_bwd");
 }
 
 // ---- training-mode batch norm of a head-tower layer (k_norm.h) ---------------------------------------------------------------
-static bool nm_shape_ok(int B, int H, int W) { return B >= 1 && H >= 1 && W >= 1; }
 size_t rd_bn_stats_workspace_bytes(int B, int H, int W, int C, int split) {
-  return nm_shape_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 3 * C * sizeof(float) : 0;
+  return bhw_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 3 * C * sizeof(float) : 0;
 }
 int rd_bn_stats(const void* z, int z_cstride, int z_coff, float* mean, float* var, int B, int H, int W, int C, int split, int dtype, void* ws,
                 size_t ws_bytes, void* stream) {
   RD_REQUIRE(z && mean && var && ws, RD_EINVAL, "bn_stats: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "bn_stats: dtype %d (RD_BF16 or RD_F16)", dtype);
   RD_REQUIRE(split >= 0, RD_EINVAL, "bn_stats: split %d (0: the library's choice)", split);
-  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "bn_stats: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "bn_stats: B %d, H %d, W %d", B, H, W);
   RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "bn_stats: C %d (8, 16, 32, 64, 128 or 256)", C);
   RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C), RD_ESHAPE, "bn_stats: channel stride and offset are multiples of 8 with coff + C <= cstride");
   RD_REQUIRE((uintptr_t)z % 16 == 0 && ((uintptr_t)mean | (uintptr_t)var | (uintptr_t)ws) % 4 == 0, RD_EINVAL,
@@ -1213,8 +1207,7 @@ int rd_bn_stats(const void* z, int z_cstride, int z_coff, float* mean, float* va
   a.z = (const unsigned short*)z; a.cs = z_cstride; a.co = z_coff; a.C = C;
   a.npix = (long)B * H * W; a.P = (int)nm_parts(a.npix, split); a.part = (float*)ws;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RD_F16) hipLaunchKernelGGL((bn_stats_partial_kernel<RD_F16>), dim3(a.P), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((bn_stats_partial_kernel<RD_BF16>), dim3(a.P), dim3(256), 0, st, a);
+  RD_LAUNCH_H16(dtype, (bn_stats_partial_kernel<DT>), dim3(a.P), dim3(256), st, a);
   hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C / 8), dim3(256), 0, st, (const float*)ws, a.P, C, a.npix, mean, var);
   return check_launch("bn_stats");
 }
@@ -1237,7 +1230,7 @@ int rd_affine_relu(const void* z, int z_cstride, int z_coff, const float* a, con
                    int B, int H, int W, int C, int dtype, void* stream) {
   RD_REQUIRE(z && a && b && y, RD_EINVAL, "affine_relu: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "affine_relu: dtype %d (RD_BF16 or RD_F16)", dtype);
-  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "affine_relu: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "affine_relu: B %d, H %d, W %d", B, H, W);
   RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "affine_relu: C %d (8, 16, 32, 64, 128 or 256)", C);
   RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(y_cstride, y_coff, C), RD_ESHAPE,
              "affine_relu: channel strides and offsets are multiples of 8 with coff + C <= cstride");
@@ -1249,13 +1242,12 @@ int rd_affine_relu(const void* z, int z_cstride, int z_coff, const float* a, con
   const long nb = nm_ew_blocks(f.npix, C);
   RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "affine_relu: %ld pixels", f.npix);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RD_F16) hipLaunchKernelGGL((affine_relu_kernel<RD_F16>), dim3((unsigned)nb), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((affine_relu_kernel<RD_BF16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  RD_LAUNCH_H16(dtype, (affine_relu_kernel<DT>), dim3((unsigned)nb), dim3(256), st, f);
   return check_launch("affine_relu");
 }
 
 size_t rd_bn_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split) {
-  return nm_shape_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 2 * C * sizeof(float) : 0;
+  return bhw_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * 2 * C * sizeof(float) : 0;
 }
 int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const float* a, const float* b,
                    const float* mean, const float* rstd, const float* gamma, int relu, void* dz, int dz_cstride, int dz_coff, float* dgamma,
@@ -1263,7 +1255,7 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
   RD_REQUIRE(g && z && mean && rstd && gamma && dz && dgamma && dbeta && ws && (!relu || (a && b)), RD_EINVAL, "bn_relu_bwd: null pointer");
   RD_REQUIRE(is_h16(dtype), RD_EINVAL, "bn_relu_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
   RD_REQUIRE(split >= 0, RD_EINVAL, "bn_relu_bwd: split %d (0: the library's choice)", split);
-  RD_REQUIRE(nm_shape_ok(B, H, W), RD_ESHAPE, "bn_relu_bwd: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "bn_relu_bwd: B %d, H %d, W %d", B, H, W);
   RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "bn_relu_bwd: C %d (8, 16, 32, 64, 128 or 256)", C);
   RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, C) && nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(dz_cstride, dz_coff, C), RD_ESHAPE,
              "bn_relu_bwd: channel strides and offsets are multiples of 8 with coff + C <= cstride");
@@ -1280,11 +1272,9 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
   const long nb = nm_ew_blocks(f.npix, C);
   RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "bn_relu_bwd: %ld pixels", f.npix);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RD_F16) hipLaunchKernelGGL((bn_bwd_partial_kernel<RD_F16>), dim3(f.P), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((bn_bwd_partial_kernel<RD_BF16>), dim3(f.P), dim3(256), 0, st, f);
+  RD_LAUNCH_H16(dtype, (bn_bwd_partial_kernel<DT>), dim3(f.P), dim3(256), st, f);
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 8, 2), dim3(256), 0, st, (const float*)ws, f.P, C, dbeta, dgamma);
-  if (dtype == RD_F16) hipLaunchKernelGGL((bn_bwd_dz_kernel<RD_F16>), dim3((unsigned)nb), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((bn_bwd_dz_kernel<RD_BF16>), dim3((unsigned)nb), dim3(256), 0, st, f);
+  RD_LAUNCH_H16(dtype, (bn_bwd_dz_kernel<DT>), dim3((unsigned)nb), dim3(256), st, f);
   return check_launch("bn_relu_bwd");
 }
 

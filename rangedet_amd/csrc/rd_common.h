@@ -212,6 +212,18 @@ template <> struct H16<RD_F16> {
   }
 };
 inline bool is_h16(int dt) { return dt == RD_BF16 || dt == RD_F16; }
+// Launch a kernel templated on the 16-bit type for a run-time dtype (checked with is_h16 before).  KERNEL names its instance with `DT`
+// for the type, in parentheses: RD_LAUNCH_H16(dtype, (some_kernel<DT, 128>), grid, block, stream, args...).
+#define RD_LAUNCH_H16(dtype, KERNEL, grid, block, stream, ...)                 \
+  do {                                                                         \
+    if ((dtype) == RD_F16) {                                                   \
+      constexpr int DT = RD_F16;                                               \
+      hipLaunchKernelGGL(KERNEL, grid, block, 0, stream, __VA_ARGS__);         \
+    } else {                                                                   \
+      constexpr int DT = RD_BF16;                                              \
+      hipLaunchKernelGGL(KERNEL, grid, block, 0, stream, __VA_ARGS__);         \
+    }                                                                          \
+  } while (0)
 inline unsigned short h16_from_f32(int dt, float v) { return dt == RD_F16 ? f32_to_f16(v) : f32_to_bf16(v); }
 inline float h16_to_f32(int dt, unsigned short h) { return dt == RD_F16 ? f16_to_f32(h) : bf16_to_f32(h); }
 
@@ -240,6 +252,30 @@ inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 typedef unsigned Slot16 __attribute__((ext_vector_type(4)));  // one 16-byte LDS/global granule (register-resident)
 
+// one slot of a 16-bit tensor <-> its eight channels in float32
+template <int DT>
+__device__ __forceinline__ void slot_unpack(const Slot16 v, float (&f)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f32x2_t_ t = H16<DT>::unpk(v[k]);
+    f[2 * k] = t[0];
+    f[2 * k + 1] = t[1];
+  }
+}
+template <int DT>
+__device__ __forceinline__ Slot16 slot_pack(const float (&f)[8]) {
+  Slot16 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = H16<DT>::pk(f[2 * k], f[2 * k + 1]);
+  return o;
+}
+// red[PL][C] in LDS, one row per pixel lane: the PL lane values of channel `tid` (tid < C) added in lane order
+__device__ __forceinline__ float lane_sum(const float* red, int PL, int C, int tid) {
+  _Pragma("clang fp contract(off)")
+  float s = red[tid];
+  for (int q = 1; q < PL; ++q) s += red[q * C + tid];
+  return s;
+}
 
 // LDS-DMA of 16 bytes per lane: LDS[lds_dst_uniform + lane*16] <- *gsrc (per lane).  Issued through inline asm on the
 // device so that hipcc's waitcnt pass does not see it: seen through the builtin, every later ds_read is preceded by

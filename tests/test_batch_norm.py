@@ -23,7 +23,7 @@ import convbwd_model as M
 import norm_model as N
 from conftest import BOTH
 from rangedet_amd import lib as R
-from test_conv_backward import DTS, back, back_image, check_hob, check_wgrad, dev16, ff, from_bits, image, rnd, same_bits, to_bits, train_inputs, vals16
+from train_util import DTS, back, back_image, check_hob, check_wgrad, dev16, ff, from_bits, image, rnd, same_bits, to_bits, train_inputs, vals16
 
 F32 = np.float32
 EPS, MOM = 1e-5 + 1e-10, 0.9

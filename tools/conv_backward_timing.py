@@ -20,32 +20,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from rangedet_amd import build, lib as rdlib  # noqa: E402
-from rangedet_amd.backward import _Ops  # noqa: E402
+from rangedet_amd.backward import TowerOps  # noqa: E402
 from rangedet_amd.runtime import TorchAllocator  # noqa: E402
+from tools.timing_util import series  # noqa: E402
 
 H, WIDTHS, C, NOUT, PEAK = 64, (2656, 1328, 664), 128, 8, 2.5e15
-
-
-def window(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def series(fns, iters, repeats):
-    """fns: {name: callable}; -> {name: median over both orders of the per-order medians}, and the raw per-order summary"""
-    names, out = list(fns), {}
-    for order in (names, names[::-1]):
-        ms = {k: [] for k in names}
-        for _ in range(repeats):
-            for k in order:
-                ms[k].append(window(fns[k], iters))
-        out["%s_first" % order[0]] = {k: dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v))) for k, v in ms.items()}
-    return {k: float(np.median([o[k]["median_ms"] for o in out.values()])) for k in names}, out
 
 
 def main():
@@ -60,7 +39,7 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(7)
     rows = []
     for dt, tdt, name in ((rdlib.RD_BF16, torch.bfloat16, "bf16"), (rdlib.RD_F16, torch.float16, "f16")):
-        ops = _Ops(dt, L, A)
+        ops = TowerOps(dt, L, A)
         for W in WIDTHS:
             n = B * H * W
             x = torch.relu(torch.randn(n, C, generator=g)).to(dev, tdt).view(B, H, W, C)          # post-ReLU activations: half zeros

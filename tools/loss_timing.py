@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 from rangedet_amd import build, lib as rdlib  # noqa: E402
 from rangedet_amd.loss import RpnLoss  # noqa: E402
 from rangedet_amd.runtime import TorchAllocator  # noqa: E402
+from tools.timing_util import series  # noqa: E402
 
 H, WP, STRIDES, NGT, NREAL = 64, 2656, (1, 2, 4), 200, 40
 
@@ -111,16 +112,6 @@ class TorchRoute:
         return out
 
 
-def window(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -155,16 +146,9 @@ def main():
     for _ in range(3):
         run_fused(), run_torch()
     torch.cuda.synchronize()
-    series = {}
-    for order in ("fused_first", "torch_first"):
-        ms = {"fused": [], "torch": []}
-        for _ in range(a.repeats):
-            for name in (("fused", "torch") if order == "fused_first" else ("torch", "fused")):
-                ms[name].append(window(run_fused if name == "fused" else run_torch, a.iters))
-        series[order] = {k: dict(median_ms=float(np.median(v)), min_ms=float(min(v)), max_ms=float(max(v))) for k, v in ms.items()}
-    med = {k: float(np.median([series[o][k]["median_ms"] for o in series])) for k in ("fused", "torch")}
+    med, raw = series({"fused": run_fused, "torch": run_torch}, a.iters, a.repeats)
     res = dict(tool="tools/loss_timing.py", source_hash=build.source_hash(), device=torch.cuda.get_device_name(0), batch=B, shape=[H, WP],
-               strides=list(STRIDES), n_gt=NGT, real_boxes=NREAL, iters=a.iters, repeats=a.repeats, series=series,
+               strides=list(STRIDES), n_gt=NGT, real_boxes=NREAL, iters=a.iters, repeats=a.repeats, series=raw,
                fused_ms=med["fused"], torch_route_ms=med["torch"], torch_over_fused=med["torch"] / med["fused"], agreement=agree)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:

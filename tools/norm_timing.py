@@ -20,9 +20,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from rangedet_amd import build, lib as rdlib  # noqa: E402
-from rangedet_amd.backward import BN_EPS, BN_MOMENTUM, _Ops  # noqa: E402
+from rangedet_amd.backward import BN_EPS, BN_MOMENTUM, TowerOps  # noqa: E402
 from rangedet_amd.runtime import TorchAllocator  # noqa: E402
-from tools.conv_backward_timing import series  # noqa: E402
+from tools.timing_util import series  # noqa: E402
 
 H, WIDTHS, C, PEAK_HBM_GBPS = 64, (2656, 1328, 664), 128, 8000.0
 
@@ -41,7 +41,7 @@ def main():
     gamma_h, beta_h = rng.uniform(0.5, 1.5, C).astype(np.float32), rng.normal(0, 0.1, C).astype(np.float32)
     rows = []
     for dt, tdt, name in ((rdlib.RD_BF16, torch.bfloat16, "bf16"), (rdlib.RD_F16, torch.float16, "f16")):
-        ops = _Ops(dt, L, A)
+        ops = TowerOps(dt, L, A)
         gamma, beta = A.upload(gamma_h), A.upload(beta_h)
         mm, mv = A.upload(np.zeros(C, np.float32)), A.upload(np.ones(C, np.float32))
         for W in WIDTHS:
