@@ -595,6 +595,52 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
                    const float* mean, const float* rstd, const float* gamma, int relu, void* dz, int dz_cstride, int dz_coff, float* dgamma,
                    float* dbeta, int B, int H, int W, int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the parameter update of the head towers: multi-tensor SGD with momentum, conv weight images re-packed on the device ---------------
+ * The reference trains with mx.optimizer `sgd`: momentum, wd, rescale_grad, clip_gradient and, under fp16, multi_precision -- float32
+ * master weights and momenta beside the 16-bit weights the network computes with (tools/train.py:306-365; OptimizeParam.optimizer in
+ * every config under config/rangedet/: momentum = 0.9, wd = 0.00001, clip_gradient = 35, rangedet_veh_wo_aug_4_18e.py:179-184).  Per
+ * element, float32, the arithmetic of MXNet's mp_sgd_mom_update operator as documented (MXNet is not available to this project: not
+ * pinned by a run of the reference):
+ *   g   = rescale_grad * grad
+ *   g   = clip_gradient >= 0 ? (g > clip ? clip : (g < -clip ? -clip : g)) : g
+ *   mom = momentum * mom - (lr_t * wd_t) * w - lr_t * g          left to right
+ *   w   = w + mom
+ * with lr_t = lr * lr_mult and wd_t = wd * wd_mult of the tensor.  Every operation is one float32 rounding in that order, nothing is
+ * fused, so the result equals a float32 restatement bit for bit.  A NaN gradient propagates; so does inf when clip_gradient < 0.
+ *
+ * All tensors of a step are listed in a table that rd_sgd_table_host writes into caller memory of rd_sgd_table_bytes bytes; the caller
+ * uploads it once (8-byte aligned) and keeps the host copy, which rd_sgd_mom_update reads for the launch geometry.  The table maps
+ * 1024-element chunks to (tensor, offset): one launch of one workgroup per chunk updates every tensor, whatever their number.  weight,
+ * grad and mom are float32 device buffers of n elements, 16-byte aligned (else RD_EINVAL; n <= 0: RD_EINVAL).  The scalars of the step
+ * are by-value arguments: a new learning rate needs no new table.
+ *
+ * A tensor that is a (cout, cin, 3, 3) conv weight with cin, cout in {64, 128} (n = 9 cout cin) may name 16-bit weight images, which a
+ * second launch over the same table rewrites from the updated weight: pack_fwd, byte for byte what rd_pack_conv3x3_ex_host(w, fold_scale,
+ * cout, cin, 1, cin, dtype) writes (fold_scale: cout device floats or NULL; the product is formed in float32, then rounded to nearest
+ * even), and pack_bwd, the image of the data gradient -- the same packer on the weight with its channel axes swapped and its taps flipped,
+ * no scale.  Each is rd_conv3x3_ex_packed_bytes(cin, cout, 1, cin) bytes, the zero tail included: the step writes all of them.  Other
+ * channel counts (the <= 16-channel body form, the 72-channel concat) and the images of other launch forms (stride-2 pair view, M16) are
+ * refused with RD_ESHAPE.  A step is two launches at most; the library allocates nothing and never synchronises; every check precedes
+ * the first launch. */
+typedef struct {
+  void* weight;             /* float32 device buffers of n elements */
+  const void* grad;
+  void* mom;
+  long n;
+  float lr_mult, wd_mult;
+  int cout, cin;            /* read only when an image is named */
+  void* pack_fwd;           /* device images, or NULL */
+  void* pack_bwd;
+  const float* fold_scale;  /* device, cout values, or NULL; needs pack_fwd */
+} rd_sgd_tensor_t;
+size_t rd_sgd_table_bytes(const rd_sgd_tensor_t* tensors, int nt);   /* 0: refused (rd_last_error_string says why) */
+int rd_sgd_table_host(const rd_sgd_tensor_t* tensors, int nt, int dtype, void* out);   /* dtype: that of the images */
+int rd_sgd_mom_update(const void* table_dev, const void* table_host, float lr, float momentum, float wd, float rescale_grad,
+                      float clip_gradient, void* stream);
+/* One image of a device-resident (cout, cin, 3, 3) float32 weight, cin, cout in {64, 128}: flip == 0 the forward image (fold_scale_dev
+ * or NULL), flip != 0 the data-gradient image (fold_scale_dev must be NULL).  One launch, the zero tail included. */
+int rd_pack_conv3x3_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin, int flip, int dtype, void* out_dev, void* stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0
 #define RD_PROF_META 1

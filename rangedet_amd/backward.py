@@ -29,6 +29,11 @@ batch's own statistics after every conv).  With z = conv3x3(x, W) rounded to the
     dbeta = sum gy, dgamma = sum gy zh
     dz = gamma rstd (gy - dbeta / n - zh dgamma / n)                batch_norm_relu_backward (rd_bn_relu_bwd)
 and dz feeds the weight and data gradients above directly.
+
+Every tower also keeps float32 master copies of its conv weights on the device next to the two 16-bit images made from them (the output
+conv's weight and bias, gamma and beta are float32 device vectors anyway), and optimizer_entries() lists each trainable parameter with
+its master, its gradient buffer and its images: rangedet_amd.optim.SGD.attach(tower) registers them, and after SGD.step() the next
+forward() and backward() run on the new weights -- no host copy, no new tower.  A tower that is never attached behaves as before.
 """
 import numpy as np
 
@@ -272,7 +277,8 @@ def batch_norm_relu_backward(g, z, saved, gamma, split=0, dtype=rdlib.RD_BF16, l
 
 class _HeadTower:
     """What the two towers share: the layer checks and the reference's parameter names, the output conv, and the forward and backward
-    loops.  A subclass supplies _layer (one layer's device parameters), _layer_forward, _dz (dL/dy -> dz of a layer) and _out_bwd_kwargs.
+    loops.  A subclass supplies _layer (one layer's device parameters), _layer_forward, _dz (dL/dy -> dz of a layer), _out_bwd_kwargs, and
+    for optimizer_entries() _fwd_image (a layer's forward image and fold scale) and _norm_entries (its trainable normalisation parameters).
     `params`: one sequence per normalisation parameter, each with one entry per conv weight; `what` names them in the refusal."""
 
     def __init__(self, conv_weights, params, what, out_weight, out_bias, kind, level, first_conv, dtype, lib, alloc):
@@ -297,7 +303,8 @@ class _HeadTower:
                 raise ValueError("%s: %d input channels after a layer with %d outputs" % (name, cin, chans))
             chans = cout
             self._stems.append(name)
-            self.layers.append(dict(self._layer(w, name, *(p[i] for p in params)), cin=cin, cout=cout, bwd=o.pack_data_grad(w)))
+            self.layers.append(dict(self._layer(w, name, *(p[i] for p in params)), cin=cin, cout=cout, bwd=o.pack_data_grad(w),
+                                    master=o.A.upload(np.ascontiguousarray(w))))
         ow = np.asarray(out_weight, np.float32)
         ow = np.ascontiguousarray(ow.reshape(ow.shape[0], -1))
         ob = np.ascontiguousarray(out_bias, dtype=np.float32)
@@ -310,6 +317,23 @@ class _HeadTower:
         self.out_names = (out_name + "_weight", out_name + "_bias")
         self.out_w, self.out_b = o.A.upload(ow), o.A.upload(ob)
         self.acts = None
+
+    def optimizer_entries(self):
+        """What rangedet_amd.optim.SGD.attach registers, one dict of SGD.add's arguments per trainable parameter: its reference name, the
+        float32 master weight and the gradient buffer backward() fills (the buffers TowerOps keys by step and layer: their addresses do not
+        depend on the input shape), and for a conv weight the two images the step re-packs from the master -- `fwd`, which forward() reads
+        (with the layer's fold scale, if it has one), and `bwd`, which the data gradient reads."""
+        o = self.ops
+        A, n = o.A, len(self.layers)
+        for i, (stem, ly) in enumerate(zip(self._stems, self.layers)):
+            shape = (ly["cout"], ly["cin"], 3, 3)
+            yield dict(name=stem + "_weight", weight=A.view_f32(ly["master"], shape), grad=A.view_f32(o.buf(("dW", i), ly["cout"] * ly["cin"] * 36), shape),
+                       pack=dict(self._fwd_image(ly), bwd=ly["bwd"][0], dtype=o.dt))
+            yield from self._norm_entries(i, stem, ly)
+        cin = self.layers[n - 1]["cout"]
+        yield dict(name=self.out_names[0], weight=A.view_f32(self.out_w, (self.nout, cin, 1, 1)),
+                   grad=A.view_f32(o.buf(("hob_dw", 0), self.nout * cin * 4), (self.nout, cin, 1, 1)))
+        yield dict(name=self.out_names[1], weight=A.view_f32(self.out_b, (self.nout,)), grad=A.view_f32(o.buf(("hob_db", 0), self.nout * 4), (self.nout,)))
 
     def forward(self, x):
         o = self.ops
@@ -370,6 +394,14 @@ class HeadTowerTrain(_HeadTower):
         return dict(fwd=o.pack_unscaled(w), gamma=_vec(o, gamma, cout, name + "_bn_gamma"), beta=_vec(o, beta, cout, name + "_bn_beta"),
                     mmean=_vec(o, mmean, cout, name + "_bn_moving_mean"), mvar=_vec(o, mvar, cout, name + "_bn_moving_var"))
 
+    def _fwd_image(self, ly):
+        return dict(fwd=ly["fwd"][0])
+
+    def _norm_entries(self, i, stem, ly):
+        o, C = self.ops, ly["cout"]
+        for key, grad in (("gamma", "bn_dgamma"), ("beta", "bn_dbeta")):
+            yield dict(name="%s_bn_%s" % (stem, key), weight=o.A.view_f32(ly[key], (C,)), grad=o.A.view_f32(o.buf((grad, i), C * 4), (C,)))
+
     def aux(self):
         A, out = self.ops.A, {}
         for name, ly in zip(self.names, self.layers):
@@ -420,6 +452,12 @@ class HeadTowerBackward(_HeadTower):
         if s.shape != (cout,) or t.shape != (cout,):
             raise ValueError("%s: scale / shift of %d values" % (name, cout))
         return dict(fwd=o.A.upload(o.L.pack_conv3x3_ex(w, 1, cin, fold_scale=s, dtype=o.dt)), shift=o.A.upload(t), scale=o.A.upload(s))
+
+    def _fwd_image(self, ly):
+        return dict(fwd=ly["fwd"], fold_scale=ly["scale"])
+
+    def _norm_entries(self, i, stem, ly):
+        return ()                      # the folded scale and shift are fixed: inference-mode normalisation has nothing to train
 
     def _layer_forward(self, i, x):
         ly = self.layers[i]

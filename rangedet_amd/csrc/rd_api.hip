@@ -13,6 +13,7 @@
 #include "k_loss.h"
 #include "k_convbwd.h"
 #include "k_norm.h"
+#include "k_optim.h"
 #include "k_sort.h"
 #include "k_wnms.h"
 
@@ -1276,6 +1277,60 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 8, 2), dim3(256), 0, st, (const float*)ws, f.P, C, dbeta, dgamma);
   RD_LAUNCH_H16(dtype, (bn_bwd_dz_kernel<DT>), dim3((unsigned)nb), dim3(256), st, f);
   return check_launch("bn_relu_bwd");
+}
+
+// ---- SGD with momentum over a table of tensors, and the conv weight images re-packed on the device (k_optim.h) ----------------------
+static int sgd_table_count(const rd_sgd_tensor_t* t, int nt, long* n_chunks, long* n_pack) {
+  RD_REQUIRE(t && nt > 0, RD_EINVAL, "sgd_table: no tensors");
+  *n_chunks = *n_pack = 0;
+  for (int i = 0; i < nt; ++i) {
+    const int rc = sgd_check_tensor(t[i], i);
+    if (rc != RD_OK) return rc;
+    *n_chunks += sgd_tensor_chunks(t[i]);
+    *n_pack += sgd_tensor_pack_chunks(t[i]);
+  }
+  RD_REQUIRE(*n_chunks <= 0x7fffffffL && *n_pack <= 0x7fffffffL && sgd_table_size(nt, *n_chunks, *n_pack) <= 0x7fffffffUL, RD_ESHAPE,
+             "sgd_table: %ld element chunks and %ld image chunks exceed one launch", *n_chunks, *n_pack);
+  return RD_OK;
+}
+size_t rd_sgd_table_bytes(const rd_sgd_tensor_t* tensors, int nt) {
+  long nc, np;
+  return sgd_table_count(tensors, nt, &nc, &np) == RD_OK ? sgd_table_size(nt, nc, np) : 0;
+}
+int rd_sgd_table_host(const rd_sgd_tensor_t* tensors, int nt, int dtype, void* out) {
+  RD_REQUIRE(out, RD_EINVAL, "sgd_table: null pointer");
+  long nc, np;
+  const int rc = sgd_table_count(tensors, nt, &nc, &np);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(np == 0 || is_h16(dtype), RD_EINVAL, "sgd_table: dtype %d of the images (RD_BF16 or RD_F16)", dtype);
+  sgd_table_build(tensors, nt, dtype, nc, np, out);
+  return RD_OK;
+}
+int rd_sgd_mom_update(const void* table_dev, const void* table_host, float lr, float momentum, float wd, float rescale_grad,
+                      float clip_gradient, void* stream) {
+  RD_REQUIRE(table_dev && table_host, RD_EINVAL, "sgd_mom_update: null pointer");
+  RD_REQUIRE((uintptr_t)table_dev % 8 == 0, RD_EINVAL, "sgd_mom_update: the device table must be 8-byte aligned");
+  SgdHeader h;
+  memcpy(&h, table_host, sizeof(h));
+  RD_REQUIRE(h.magic == SGD_MAGIC && h.nt > 0 && h.n_chunks > 0 && h.n_pack >= 0 && h.bytes == sgd_table_size(h.nt, h.n_chunks, h.n_pack) &&
+             (h.n_pack == 0 || is_h16(h.dtype)), RD_EINVAL, "sgd_mom_update: table_host is not a table of rd_sgd_table_host");
+  hipStream_t st = (hipStream_t)stream;
+  const SgdStep s{lr, momentum, wd, rescale_grad, clip_gradient};
+  hipLaunchKernelGGL(sgd_mom_kernel, dim3((unsigned)h.n_chunks), dim3(256), 0, st, (const unsigned char*)table_dev, s);
+  if (h.n_pack > 0) RD_LAUNCH_H16(h.dtype, (sgd_pack_kernel<DT>), dim3((unsigned)h.n_pack), dim3(256), st, (const unsigned char*)table_dev);
+  return check_launch("sgd_mom_update");
+}
+int rd_pack_conv3x3_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin, int flip, int dtype, void* out_dev, void* stream) {
+  RD_REQUIRE(w_dev && out_dev, RD_EINVAL, "pack_conv3x3_dev: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_conv3x3_dev: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(sgd_pack_shape_ok(cout, cin), RD_ESHAPE, "pack_conv3x3_dev: %d -> %d channels (64 or 128 on either side)", cin, cout);
+  RD_REQUIRE(!(flip && fold_scale_dev), RD_EINVAL, "pack_conv3x3_dev: the data-gradient image takes no fold scale");
+  RD_REQUIRE((uintptr_t)out_dev % 16 == 0 && ((uintptr_t)w_dev | (uintptr_t)fold_scale_dev) % 4 == 0, RD_EINVAL,
+             "pack_conv3x3_dev: the image must be 16-byte aligned, the float buffers 4-byte aligned");
+  const unsigned grid = (unsigned)((sgd_image_slots(cout, cin) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS);
+  RD_LAUNCH_H16(dtype, (pack_conv3x3_dev_kernel<DT>), dim3(grid), dim3(256), (hipStream_t)stream, w_dev, fold_scale_dev, cout, cin, flip ? 1 : 0,
+                (unsigned short*)out_dev);
+  return check_launch("pack_conv3x3_dev");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------

@@ -151,10 +151,20 @@ SIGNATURES = {
     "rd_bn_relu_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rd_bn_relu_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_void_p,
                                c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_sgd_table_bytes": (c_size_t, [c_void_p, c_int]),
+    "rd_sgd_table_host": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "rd_sgd_mom_update": (c_int, [c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    "rd_pack_conv3x3_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rd_prof_enable": (c_int, [c_int]),
     "rd_prof_reset": (c_int, []),
     "rd_prof_get": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_long)]),
 }
+
+
+class SgdTensor(ctypes.Structure):
+    """rd_sgd_tensor_t (include/rangedet_hip.h): one tensor of an SGD step"""
+    _fields_ = [("weight", c_void_p), ("grad", c_void_p), ("mom", c_void_p), ("n", c_long), ("lr_mult", c_float), ("wd_mult", c_float),
+                ("cout", c_int), ("cin", c_int), ("pack_fwd", c_void_p), ("pack_bwd", c_void_p), ("fold_scale", c_void_p)]
 
 
 class RangeDetError(RuntimeError):
@@ -309,6 +319,14 @@ class Lib:
         assert arrs[0].shape == (32, 3) and arrs[2].shape == (64, 32) and arrs[6].shape == (64, 576)
         out = np.zeros(self.cdll.rd_meta_packed_bytes(dtype), dtype=np.uint8)
         self.call("rd_pack_meta_host", *[a.ctypes.data for a in arrs], dtype, out.ctypes.data)
+        return out
+
+    def sgd_table(self, tensors, dtype=RD_BF16):
+        """tensors: a sequence of SgdTensor -> the table of rd_sgd_mom_update as host bytes (upload it, keep it)"""
+        arr = (SgdTensor * len(tensors))(*tensors)
+        nbytes = self.cdll.rd_sgd_table_bytes(ctypes.addressof(arr), len(tensors))
+        out = np.zeros(max(nbytes, 8), dtype=np.uint8)
+        self.call("rd_sgd_table_host", ctypes.addressof(arr), len(tensors), dtype, out.ctypes.data)   # raises with the refusal's own code
         return out
 
     def wnms_order_host(self, dets):
