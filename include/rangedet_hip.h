@@ -539,6 +539,15 @@ int rd_relu_affine_bwd(const void* g, int g_cstride, int g_coff, const void* y, 
 size_t rd_conv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split);
 int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
                           int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* dW (cout, cin) float32 of a stride-1 1x1 conv (the projection shortcut of a backbone BasicBlock): dW[co,ci] = sum_{b,h,w} dz[b,h,w,co]
+ * x[b,h,w,ci], cin, cout in {64, 128} (else RD_ESHAPE), any B, H, W >= 1; fp32 accumulation on the matrix cores over the flat pixel axis in
+ * tiles of 64 pixels.  A workgroup owns all cout x cin outputs and a contiguous run of tiles, so every input byte is read once.  split:
+ * the most partial sums per output element (= workgroups); 0: the library's choice, min(512, ceil(tiles / 8)).  The workspace holds
+ * split x cout x cin floats at most; split, the absence of atomics and the determinism are those of rd_conv3x3_bwd_weight.  The data
+ * gradient of the 1x1 conv is rd_conv2d_bn_act with kh = kw = 1 on the transposed weight packed by rd_pack_conv_weight_host. */
+size_t rd_conv1x1_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split);
+int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                          int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 /* Backward of rd_head_out.  d_out: float32 at d_out[b*out_batch_stride + (n_off + h*W + w)*nout + o], exactly as rd_head_out writes `out`
  * -- so rd_rpn_loss's flat d_logit / d_delta buffers are read in place.  x: the output conv's input (the post-ReLU output of the last
  * tower conv), w (nout, cin) float32.  nout 1..8, cin 64 or 128 (else RD_ESHAPE).
@@ -594,6 +603,33 @@ size_t rd_bn_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split);
 int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const float* a, const float* b,
                    const float* mean, const float* rstd, const float* gamma, int relu, void* dz, int dz_cstride, int dz_coff, float* dgamma,
                    float* dbeta, int B, int H, int W, int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* The residual form: the second BatchNorm of a backbone BasicBlock (rangedet/symbol/backbone/dla_backbone.py:18-56: conv2 -> BN -> + shortcut
+ * -> ReLU).  r is the shortcut in the activation type, a channels-last tensor with its own channel stride and offset: the block input
+ * (identity shortcut, ar = br = NULL) or the 16-bit output zs of the 1x1 projection conv, whose own BatchNorm is folded into ar, br
+ * (rd_bn_stats and rd_bn_fold on zs).  Per element, float32, every operation not written fmaf rounded on its own:
+ *   t = fmaf(z, a, b);  u = ar ? fmaf(r, ar, br) : (float)r;  v = t + u;  y = round(relu ? max(v, 0) : v)
+ * y may be z.  C, alignment and the status codes are those of rd_affine_relu; ar without br (or the reverse) is RD_EINVAL. */
+int rd_affine_add_relu(const void* z, int z_cstride, int z_coff, const float* a, const float* b, const void* r, int r_cstride, int r_coff,
+                       const float* ar, const float* br, int relu, void* y, int y_cstride, int y_coff, int B, int H, int W, int C, int dtype,
+                       void* stream);
+/* Its backward, three launches like rd_bn_relu_bwd: ONE sweep over g, z and r gives the two (identity) or three (projection) partial sums
+ * per channel, a fixed-tree launch adds them, one elementwise launch writes dz and dr together.  g = dL/dy; a, b, mean, rstd, gamma of the
+ * main branch and, for a projection shortcut, ar, br, mean_r, rstd_r, gamma_r of the shortcut's BatchNorm -- these five and the outputs
+ * dgamma_r, dbeta_r are all given or all NULL (else RD_EINVAL).
+ *   m = [fmaf(z, a, b) + u > 0]   with u and the sum formed exactly as rd_affine_add_relu forms v; y is not read
+ *   gy = m ? g : 0;  zh = (z - mean) * rstd;  dbeta = sum gy;  dgamma = sum fmaf(gy, zh, .)
+ *   c1 = dbeta / (float)n;  c2 = dgamma / (float)n;  dz = round(gamma * rstd * fmaf(-zh, c2, gy - c1))
+ *   identity:    dr = gy                                             (the bits of g, or +0)
+ *   projection:  zhr = (r - mean_r) * rstd_r;  dgamma_r = sum fmaf(gy, zhr, .);  dbeta_r = dbeta (the same bytes)
+ *                dr = round(gamma_r * rstd_r * fmaf(-zhr, dgamma_r / (float)n, gy - c1))
+ * The partial count is that of rd_bn_relu_bwd (min(split or 1024, ceil(n / 64))), the workspace holds 2 or 3 x that x C floats
+ * (projection != 0: 3); no atomics, two calls give the same bytes.  dz may be g. */
+size_t rd_bn_add_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split, int projection);
+int rd_bn_add_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const void* r, int r_cstride,
+                       int r_coff, const float* a, const float* b, const float* mean, const float* rstd, const float* gamma, const float* ar,
+                       const float* br, const float* mean_r, const float* rstd_r, const float* gamma_r, void* dz, int dz_cstride, int dz_coff,
+                       void* dr, int dr_cstride, int dr_coff, float* dgamma, float* dbeta, float* dgamma_r, float* dbeta_r, int B, int H, int W,
+                       int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- the parameter update of the head towers: multi-tensor SGD with momentum, conv weight images re-packed on the device ---------------
  * The reference trains with mx.optimizer `sgd`: momentum, wd, rescale_grad, clip_gradient and, under fp16, multi_precision -- float32
@@ -620,7 +656,10 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
  * even), and pack_bwd, the image of the data gradient -- the same packer on the weight with its channel axes swapped and its taps flipped,
  * no scale.  Each is rd_conv3x3_ex_packed_bytes(cin, cout, 1, cin) bytes, the zero tail included: the step writes all of them.  Other
  * channel counts (the <= 16-channel body form, the 72-channel concat) and the images of other launch forms (stride-2 pair view, M16) are
- * refused with RD_ESHAPE.  A step is two launches at most; the library allocates nothing and never synchronises; every check precedes
+ * refused with RD_ESHAPE.  A (cout, cin, 1, 1) weight of the same channel counts (n = cout cin: the tap count of an entry follows from n)
+ * may name images too: pack_fwd, byte for byte what rd_pack_conv_weight_host(w, cout, cin, 1, 1, dtype) writes (rd_conv_packed_bytes(1, cin,
+ * cout, dtype) bytes, zero tail included), and pack_bwd, the same packer on the transposed (cin, cout) weight: what rd_conv2d_bn_act with
+ * kh = kw = 1 reads for the conv and for its data gradient.  A step is two launches at most; the library allocates nothing and never synchronises; every check precedes
  * the first launch. */
 typedef struct {
   void* weight;             /* float32 device buffers of n elements */

@@ -1,0 +1,242 @@
+"""A backbone BasicBlock in training mode on the device: the step below rangedet_amd.backward's towers.  The DLA backbone is built almost
+entirely of `basicblock` units (rangedet_amd/symbol/backbone/dla_backbone.py:31-45, the reference's dla_backbone.py:18-56):
+
+    conv1 3x3 -> BN -> ReLU -> conv2 3x3 -> BN -> (+ shortcut) -> ReLU        shortcut: the block input, or BN(conv 1x1) of it
+
+every BatchNorm with the batch's own statistics (normalizer_factory(type="localbn")).  BasicBlockTrain runs one stride-1 block at 64 or
+128 channels forward and backward, ResStageTrain a list of them; with x the input, n = B H W, all arithmetic float32 (csrc/k_norm.h):
+
+    forward   z1 = conv3x3(x, W1); a1, b1 = fold(stats(z1)); y1 = relu(a1 z1 + b1)              conv_unscaled, bn_stats, bn_fold, affine_relu
+              z2 = conv3x3(y1, W2); a2, b2 = fold(stats(z2))
+              zs = conv1x1(x, Ws); as, bs = fold(stats(zs))                                      projection only
+              y = relu(a2 z2 + b2 + u),  u = x  or  as zs + bs                                   affine_add_relu (rd_affine_add_relu)
+    backward  dz2, dr, dgamma2, dbeta2 (, dgamma_s, dbeta_s) from g = dL/dy, z2 and r = x or zs  bn_add_relu_bwd (rd_bn_add_relu_bwd)
+              dW2 = weight_grad(y1, dz2); g1 = data_grad(dz2, W2)
+              dz1, dgamma1, dbeta1 = bn_relu_bwd(g1, z1)
+              dW1 = weight_grad(x, dz1)
+              dWs = weight_grad1x1(x, dr); ds = conv1x1(dr, Ws transposed)                       projection only
+              dx = data_grad(dz1, W1) + (dr or ds)                                               data_grad_add: the add is in that launch's epilogue
+
+The last step passes the shortcut gradient as the persistent conv launch's residual with RD_SCALE_FOLDED | RD_ADD and no ReLU: one float32
+add on the accumulator, one rounding (the launch takes that flag combination at every shape: its epilogue reads the flags it is given).
+Everything runs on the allocator's current stream without a host synchronisation; buffers are reused between calls of the same shape.
+A block keeps float32 masters and both 16-bit images of each conv weight on the device, and optimizer_entries() lists every trainable
+parameter the way the towers do: rangedet_amd.optim.SGD.attach(block) registers them and the forward() after a step() runs on the new
+weights.  Refused with NotImplementedError: strided blocks (unit 1 of res2a .. res3), fewer than 64 input channels (res1_unit1), the
+Meta-Kernel unit, channel counts outside {64, 128}, an identity shortcut between different channel counts.
+"""
+import numpy as np
+
+from . import lib as rdlib
+from .backward import BN_EPS, BN_MOMENTUM, TowerOps, _check16, _ops, _vec
+
+_BN_KEYS = ("gamma", "beta", "moving_mean", "moving_var")
+
+
+# ---- the single steps as functions (host parameters are uploaded on every call: keep a BasicBlockTrain for repeated use) ----------------------
+def batch_norm_add_relu_forward(z, a, b, r, ar=None, br=None, relu=True, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """y = relu(fmaf(z, a, b) + u), u = r or fmaf(r, ar, br); a, b (and ar, br) float32 host vectors of C values"""
+    o = _ops(dtype, lib, alloc)
+    C = int(z.shape[3])
+    av, bv = _vec(o, a, C, "a"), _vec(o, b, C, "b")
+    arv, brv = (None, None) if ar is None else (_vec(o, ar, C, "ar"), _vec(o, br, C, "br"))
+    return o.affine_add_relu(z, av, bv, r, arv, brv, relu)
+
+
+def batch_norm_add_relu_backward(g, z, r, saved, gamma, saved_r=None, gamma_r=None, split=0, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """g = dL/dy; saved (and saved_r for a projection shortcut): dicts of the device buffers a, b, mean, rstd as batch_norm_relu_forward
+    returns them; gamma (gamma_r) float32 host vectors -> (dz, dr, dgamma, dbeta, dgamma_r, dbeta_r), the last two None without saved_r"""
+    o = _ops(dtype, lib, alloc)
+    C = int(z.shape[3])
+    return o.bn_add_relu_bwd(g, z, r, saved, _vec(o, gamma, C, "gamma"), saved_r, None if saved_r is None else _vec(o, gamma_r, C, "gamma_r"), split)
+
+
+def conv1x1_weight_grad(x, dz, dtype=rdlib.RD_BF16, split=0, lib=None, alloc=None):
+    """dL/dW (cout, cin, 1, 1) float32 of a stride-1 1x1 conv from its input x and dz; deterministic"""
+    return _ops(dtype, lib, alloc).weight_grad1x1(x, dz, split=split)
+
+
+def conv1x1_data_grad(dz, w_oi, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """dL/dx of a stride-1 1x1 conv: the 1x1 forward launch on the transposed weight"""
+    o = _ops(dtype, lib, alloc)
+    w = np.asarray(w_oi, np.float32).reshape(w_oi.shape[0], -1)
+    return o.conv1x1(dz, o.pack_conv1x1(np.ascontiguousarray(w.T)), w.shape[0], w.shape[1], ("ds", 0))
+
+
+def _bn_params(bn, what):
+    if isinstance(bn, dict):
+        missing = [k for k in _BN_KEYS if k not in bn]
+        if missing:
+            raise ValueError("%s: missing %s (a dict of gamma, beta, moving_mean, moving_var)" % (what, ", ".join(missing)))
+        return tuple(bn[k] for k in _BN_KEYS)
+    if bn is None or len(bn) != 4:
+        raise ValueError("%s: (gamma, beta, moving_mean, moving_var)" % what)
+    return tuple(bn)
+
+
+class BasicBlockTrain:
+    """One stride-1 BasicBlock as the reference trains it.
+      name               the unit's name in the graph (res2a_unit2, agg1_res_unit1, ...): parameters are <name>_conv1_weight, <name>_bn1_gamma|beta,
+                         <name>_conv2_weight, <name>_bn2_gamma|beta and, with a projection, <name>_sc_weight, <name>_sc_bn_gamma|beta
+      conv1_w, conv2_w   (cout, cin, 3, 3) and (cout, cout, 3, 3) float32
+      bn1, bn2, sc_bn    (gamma, beta, moving_mean, moving_var) or a dict of these: cout values each; the moving statistics are copied to the
+                         device once and updated there by every forward()
+      sc_w               (cout, cin[, 1, 1]) for a projection shortcut (with sc_bn), None for an identity one
+      stride, meta_kernel   what the graph says of the unit; anything but (1, 1) / False is refused
+    forward(x) -> y; backward(g) -> (dx, {reference parameter name: float32 gradient}); aux() -> {name: float32 device vector} of the
+    moving statistics.  Keeps x, z1, y1, z2, zs and the folded vectors (self.saved) from forward(), and g, dz2, dr, g1, dz1, ds, dx from
+    backward()."""
+
+    def __init__(self, name, conv1_w, conv2_w, bn1, bn2, sc_w=None, sc_bn=None, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM,
+                 stride=(1, 1), meta_kernel=False, lib=None, alloc=None):
+        self.name = name
+        if meta_kernel or conv1_w is None:
+            raise NotImplementedError("%s: a Meta-Kernel unit -- its first conv is the Meta-Kernel, which has no backward here" % name)
+        if tuple(stride) != (1, 1):
+            raise NotImplementedError("%s: stride %r -- the strided conv2 and the strided shortcut (unit 1 of res2a .. res3) have no backward here"
+                                      % (name, tuple(stride)))
+        w1, w2 = np.asarray(conv1_w, np.float32), np.asarray(conv2_w, np.float32)
+        if w1.ndim != 4 or w1.shape[2:] != (3, 3) or w2.ndim != 4 or w2.shape[2:] != (3, 3):
+            raise ValueError("%s: conv1 and conv2 are (cout, cin, 3, 3) weights, got %r and %r" % (name, w1.shape, w2.shape))
+        cout, cin = w1.shape[:2]
+        if cin < 64:
+            raise NotImplementedError("%s: %d input channels -- fewer than 64 input channels (res1_unit1: the <= 16-channel body form) has no "
+                                      "backward here" % (name, cin))
+        if cin not in (64, 128) or cout not in (64, 128):
+            raise NotImplementedError("%s: %d -> %d channels; the backward kernels run 64 or 128 on either side" % (name, cin, cout))
+        if w2.shape[:2] != (cout, cout):
+            raise ValueError("%s: conv2 %r after a conv1 with %d outputs" % (name, w2.shape, cout))
+        if sc_w is None and cin != cout:
+            raise NotImplementedError("%s: an identity shortcut from %d to %d channels -- different channel counts need the projection "
+                                      "(sc_w, sc_bn)" % (name, cin, cout))
+        if (sc_w is None) != (sc_bn is None):
+            raise ValueError("%s: sc_w and sc_bn go together" % name)
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        self.cin, self.cout, self.proj = cin, cout, sc_w is not None
+        self.eps, self.momentum = float(eps), float(momentum)
+        A = o.A
+        self.convs = {"conv1": dict(cin=cin, cout=cout, fwd=o.pack_unscaled(w1), bwd=o.pack_data_grad(w1), master=A.upload(np.ascontiguousarray(w1))),
+                      "conv2": dict(cin=cout, cout=cout, fwd=o.pack_unscaled(w2), bwd=o.pack_data_grad(w2), master=A.upload(np.ascontiguousarray(w2)))}
+        self.bns = {"bn1": self._bn(bn1, "bn1"), "bn2": self._bn(bn2, "bn2")}
+        if self.proj:
+            ws = np.asarray(sc_w, np.float32)
+            ws = np.ascontiguousarray(ws.reshape(ws.shape[0], -1))
+            if ws.shape != (cout, cin):
+                raise ValueError("%s: the projection is a (%d, %d[, 1, 1]) weight, got %r" % (name, cout, cin, np.asarray(sc_w).shape))
+            self.convs["sc"] = dict(cin=cin, cout=cout, fwd=o.pack_conv1x1(ws), bwd=o.pack_conv1x1(np.ascontiguousarray(ws.T)), master=A.upload(ws))
+            self.bns["sc_bn"] = self._bn(sc_bn, "sc_bn")
+        self.x = self.saved = None
+
+    def _bn(self, bn, key):
+        o, C = self.ops, self.cout
+        what = "%s_%s" % (self.name, key)
+        return {k: _vec(o, v, C, "%s_%s" % (what, k)) for k, v in zip(_BN_KEYS, _bn_params(bn, what))}
+
+    def _norm(self, z, key, tag, unbiased):
+        o, bn = self.ops, self.bns[key]
+        mean, var = o.bn_stats(z, tag=tag)
+        rstd, a, b = o.bn_fold(mean, var, bn["gamma"], bn["beta"], bn["moving_mean"], bn["moving_var"], int(np.prod(z.shape[:3])), self.cout,
+                               self.eps, self.momentum, unbiased, tag=tag)
+        return dict(a=a, b=b, mean=mean, var=var, rstd=rstd)
+
+    def forward(self, x, unbiased=True):
+        o, cv = self.ops, self.convs
+        if _check16(x, "x")[3] != self.cin:
+            raise ValueError("%s: %d input channels, conv1 takes %d" % (self.name, int(x.shape[3]), self.cin))
+        saved = {}
+        z1 = o.conv_unscaled(x, cv["conv1"]["fwd"], self.cin, self.cout, tag=1)
+        saved["bn1"] = self._norm(z1, "bn1", 1, unbiased)
+        y1 = o.affine_relu(z1, saved["bn1"]["a"], saved["bn1"]["b"], tag=1)
+        z2 = o.conv_unscaled(y1, cv["conv2"]["fwd"], self.cout, self.cout, tag=2)
+        saved["bn2"] = self._norm(z2, "bn2", 2, unbiased)
+        zs = None
+        if self.proj:
+            zs = o.conv1x1(x, cv["sc"]["fwd"], self.cin, self.cout, ("zs", 0))
+            saved["sc_bn"] = self._norm(zs, "sc_bn", "s", unbiased)
+        s2, ss = saved["bn2"], saved.get("sc_bn")
+        y = o.affine_add_relu(z2, s2["a"], s2["b"], zs if self.proj else x, ss and ss["a"], ss and ss["b"])
+        self.x, self.z1, self.y1, self.z2, self.zs, self.saved, self.y = x, z1, y1, z2, zs, saved, y
+        return y
+
+    def backward(self, g):
+        if self.x is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
+        o, cv, bn, sv, nm = self.ops, self.convs, self.bns, self.saved, self.name
+        grads = {}
+        r = self.zs if self.proj else self.x
+        dz2, dr, grads[nm + "_bn2_gamma"], grads[nm + "_bn2_beta"], dgs, dbs = o.bn_add_relu_bwd(
+            g, self.z2, r, sv["bn2"], bn["bn2"]["gamma"], sv.get("sc_bn"), bn["sc_bn"]["gamma"] if self.proj else None, tag=2)
+        grads[nm + "_conv2_weight"] = o.weight_grad(self.y1, dz2, tag=2)
+        g1 = o.data_grad(dz2, cv["conv2"]["bwd"], tag=2)
+        dz1, grads[nm + "_bn1_gamma"], grads[nm + "_bn1_beta"] = o.bn_relu_bwd(g1, self.z1, sv["bn1"], bn["bn1"]["gamma"], tag=1)
+        grads[nm + "_conv1_weight"] = o.weight_grad(self.x, dz1, tag=1)
+        ds = None
+        if self.proj:
+            grads[nm + "_sc_bn_gamma"], grads[nm + "_sc_bn_beta"] = dgs, dbs
+            grads[nm + "_sc_weight"] = o.weight_grad1x1(self.x, dr, tag="s")
+            ds = o.conv1x1(dr, cv["sc"]["bwd"], self.cout, self.cin, ("ds", 0))
+        dx = o.data_grad_add(dz1, cv["conv1"]["bwd"], ds if self.proj else dr, tag=1)
+        self.g, self.dz2, self.dr, self.g1, self.dz1, self.ds, self.dx = g, dz2, dr, g1, dz1, ds, dx
+        return dx, grads
+
+    def aux(self):
+        A, out = self.ops.A, {}
+        for key, bn in self.bns.items():
+            out["%s_%s_moving_mean" % (self.name, key)] = A.view_f32(bn["moving_mean"], (self.cout,))
+            out["%s_%s_moving_var" % (self.name, key)] = A.view_f32(bn["moving_var"], (self.cout,))
+        return out
+
+    def optimizer_entries(self):
+        """one dict of SGD.add's arguments per trainable parameter: its reference name, the float32 master, the gradient buffer backward()
+        fills (keyed by step and tag: its address does not depend on the input shape) and, for a conv weight, the two images a step re-packs"""
+        o, nm = self.ops, self.name
+        A = o.A
+        for key, bkey, tag in (("conv1", "bn1", 1), ("conv2", "bn2", 2)):
+            cv = self.convs[key]
+            shape = (cv["cout"], cv["cin"], 3, 3)
+            yield dict(name="%s_%s_weight" % (nm, key), weight=A.view_f32(cv["master"], shape),
+                       grad=A.view_f32(o.buf(("dW", tag), cv["cout"] * cv["cin"] * 36), shape), pack=dict(fwd=cv["fwd"][0], bwd=cv["bwd"][0], dtype=o.dt))
+            yield from self._norm_entries(bkey, ("bn_dgamma", tag), ("bn_dbeta", tag))
+        if self.proj:
+            cv = self.convs["sc"]
+            shape = (cv["cout"], cv["cin"], 1, 1)
+            yield dict(name=nm + "_sc_weight", weight=A.view_f32(cv["master"], shape),
+                       grad=A.view_f32(o.buf(("dW1", "s"), cv["cout"] * cv["cin"] * 4), shape), pack=dict(fwd=cv["fwd"], bwd=cv["bwd"], dtype=o.dt))
+            yield from self._norm_entries("sc_bn", ("bn_dgamma_r", 2), ("bn_dbeta_r", 2))
+
+    def _norm_entries(self, bkey, gkey, bkey_grad):
+        o, C = self.ops, self.cout
+        for k, grad in (("gamma", gkey), ("beta", bkey_grad)):
+            yield dict(name="%s_%s_%s" % (self.name, bkey, k), weight=o.A.view_f32(self.bns[bkey][k], (C,)), grad=o.A.view_f32(o.buf(grad, C * 4), (C,)))
+
+
+class ResStageTrain:
+    """A run of BasicBlockTrain units: forward through the list, backward in reverse with each block's dx fed to the one before it; the
+    gradient dicts merged, optimizer_entries() and aux() chained."""
+
+    def __init__(self, blocks):
+        self.blocks = list(blocks)
+        if not self.blocks:
+            raise ValueError("ResStageTrain: at least one block")
+
+    def forward(self, x, unbiased=True):
+        for b in self.blocks:
+            x = b.forward(x, unbiased)
+        return x
+
+    def backward(self, g):
+        grads = {}
+        for b in reversed(self.blocks):
+            g, gb = b.backward(g)
+            grads.update(gb)
+        return g, grads
+
+    def optimizer_entries(self):
+        for b in self.blocks:
+            yield from b.optimizer_entries()
+
+    def aux(self):
+        out = {}
+        for b in self.blocks:
+            out.update(b.aux())
+        return out

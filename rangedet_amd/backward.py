@@ -34,6 +34,9 @@ Every tower also keeps float32 master copies of its conv weights on the device n
 conv's weight and bias, gamma and beta are float32 device vectors anyway), and optimizer_entries() lists each trainable parameter with
 its master, its gradient buffer and its images: rangedet_amd.optim.SGD.attach(tower) registers them, and after SGD.step() the next
 forward() and backward() run on the new weights -- no host copy, no new tower.  A tower that is never attached behaves as before.
+
+TowerOps also holds the steps of a backbone BasicBlock (the residual batch norm forward and backward, the 1x1 conv, its weight gradient, the
+data gradient with a residual added in its epilogue): rangedet_amd.backbone_train builds BasicBlockTrain and ResStageTrain from them.
 """
 import numpy as np
 
@@ -200,6 +203,82 @@ class TowerOps:
         L.call("rd_bn_relu_bwd", rdlib.ptr(g), C, 0, rdlib.ptr(z), C, 0, A.ptr(saved["a"]), A.ptr(saved["b"]), A.ptr(saved["mean"]), A.ptr(saved["rstd"]),
                A.ptr(gamma), 1 if relu else 0, A.ptr(dz), C, 0, A.ptr(dg), A.ptr(db), B, H, W, C, split, self.dt, A.ptr(ws), nws, _stream(A))
         return _view16(A, dz, (B, H, W, C), self.dt), A.view_f32(dg, (C,)), A.view_f32(db, (C,))
+
+    # ---- the residual BatchNorm and the 1x1 conv of a backbone BasicBlock (rangedet_amd.backbone_train) ------------------------------------
+    def affine_add_relu(self, z, a, b, r, ar=None, br=None, relu=True, tag=0):
+        """y = relu(fmaf(z, a, b) + u), u = r (identity shortcut) or fmaf(r, ar, br) (projection); z, r (B, H, W, C)"""
+        A = self.A
+        B, H, W, C = _check16(z, "z")
+        if _check16(r, "r") != (B, H, W, C):
+            raise ValueError("affine_add_relu: z %r and r %r differ" % (tuple(z.shape), tuple(r.shape)))
+        out = self.buf(("bn_add_y", tag), B * H * W * C * 2)
+        self.L.call("rd_affine_add_relu", rdlib.ptr(z), C, 0, A.ptr(a), A.ptr(b), rdlib.ptr(r), C, 0, None if ar is None else A.ptr(ar),
+                    None if br is None else A.ptr(br), 1 if relu else 0, A.ptr(out), C, 0, B, H, W, C, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, C), self.dt)
+
+    def bn_add_relu_bwd(self, g, z, r, saved, gamma, saved_r=None, gamma_r=None, split=0, tag=0):
+        """g, z, r (B, H, W, C); saved (and, for a projection shortcut, saved_r): the dicts of buffers a, b, mean, rstd the forward kept ->
+        dz, dr, dgamma, dbeta, and dgamma_r, dbeta_r (None for an identity shortcut)"""
+        A, L = self.A, self.L
+        B, H, W, C = _check16(z, "z")
+        if _check16(g, "g") != (B, H, W, C) or _check16(r, "r") != (B, H, W, C):
+            raise ValueError("bn_add_relu_bwd: g %r, z %r and r %r differ" % (tuple(g.shape), tuple(z.shape), tuple(r.shape)))
+        proj = saved_r is not None
+        nws = L.raw("rd_bn_add_relu_bwd_workspace_bytes")(B, H, W, C, split, 1 if proj else 0)
+        if not nws:
+            raise NotImplementedError("rd_bn_add_relu_bwd: %d channels (8, 16, 32, 64, 128 or 256) with split %d" % (C, split))
+        ws = self.buf(("norm_ws", 0), nws)
+        dz, dr = self.buf(("bn_add_dz", tag), B * H * W * C * 2), self.buf(("bn_add_dr", tag), B * H * W * C * 2)
+        dg, db = self.buf(("bn_dgamma", tag), C * 4), self.buf(("bn_dbeta", tag), C * 4)
+        dgr, dbr = (self.buf(("bn_dgamma_r", tag), C * 4), self.buf(("bn_dbeta_r", tag), C * 4)) if proj else (None, None)
+        sr = [A.ptr(saved_r[k]) for k in ("a", "b", "mean", "rstd")] + [A.ptr(gamma_r)] if proj else [None] * 5
+        L.call("rd_bn_add_relu_bwd", rdlib.ptr(g), C, 0, rdlib.ptr(z), C, 0, rdlib.ptr(r), C, 0, A.ptr(saved["a"]), A.ptr(saved["b"]),
+               A.ptr(saved["mean"]), A.ptr(saved["rstd"]), A.ptr(gamma), *sr, A.ptr(dz), C, 0, A.ptr(dr), C, 0, A.ptr(dg), A.ptr(db),
+               None if dgr is None else A.ptr(dgr), None if dbr is None else A.ptr(dbr), B, H, W, C, split, self.dt, A.ptr(ws), nws, _stream(A))
+        v16, vf = (lambda b_: _view16(A, b_, (B, H, W, C), self.dt)), (lambda b_: None if b_ is None else A.view_f32(b_, (C,)))
+        return v16(dz), v16(dr), vf(dg), vf(db), vf(dgr), vf(dbr)
+
+    def pack_conv1x1(self, w_oi):
+        """the image rd_conv2d_bn_act reads for a 1x1 conv with the (cout, cin) weight: no scale, one tap"""
+        w = np.ascontiguousarray(np.asarray(w_oi, np.float32).reshape(w_oi.shape[0], -1))
+        return self.A.upload(self.L.pack_conv_weight(w.reshape(w.shape + (1, 1)), self.dt))
+
+    def conv1x1(self, x, image, cin, cout, key):
+        """x (B, H, W, cin) -> conv1x1(x, W) rounded to the activation type, in the buffer `key`; image = pack_conv1x1(W).  With the image of
+        the transposed weight this is the 1x1 conv's data gradient."""
+        A = self.A
+        B, H, W = _check16(x, "x")[:3]
+        out = self.buf(key, B * H * W * cout * 2)
+        self.L.call("rd_conv2d_bn_act", rdlib.ptr(x), cin, 0, A.ptr(image), None, None, None, 0, 0, A.ptr(out), cout, 0, B, H, W, cin, cout, 1, 1,
+                    1, 0, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, cout), self.dt)
+
+    def weight_grad1x1(self, x, dz, tag=0, split=0):
+        """x (B, H, W, cin), dz (B, H, W, cout) -> dW (cout, cin, 1, 1) float32"""
+        A, L = self.A, self.L
+        B, H, W, cin = _check16(x, "x")
+        if _check16(dz, "dz")[:3] != (B, H, W):
+            raise ValueError("weight_grad1x1: x %r and dz %r differ in B, H or W" % (tuple(x.shape), tuple(dz.shape)))
+        cout = int(dz.shape[3])
+        if cin not in (64, 128) or cout not in (64, 128):
+            raise NotImplementedError("weight_grad1x1: %d -> %d channels; the kernel runs 64 or 128 on either side" % (cin, cout))
+        nws = L.raw("rd_conv1x1_bwd_weight_workspace_bytes")(B, H, W, cin, cout, split)
+        ws, out = self.buf(("bww_ws", 0), nws), self.buf(("dW1", tag), cout * cin * 4)
+        L.call("rd_conv1x1_bwd_weight", rdlib.ptr(x), cin, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, W, cin, cout, split, self.dt, A.ptr(ws),
+               nws, _stream(A))
+        return A.view_f32(out, (cout, cin, 1, 1))
+
+    def data_grad_add(self, dz, packed, residual, tag=0):
+        """data_grad with `residual` (B, H, W, cin) added in the launch's epilogue: one float32 add, one rounding (RD_ADD, no ReLU)"""
+        A = self.A
+        img, zero_shift, cin = packed
+        B, H, W, cout = _check16(dz, "dz")
+        if _check16(residual, "residual") != (B, H, W, cin):
+            raise ValueError("data_grad_add: residual %r, the input gradient is %r" % (tuple(residual.shape), (B, H, W, cin)))
+        out = self.buf(("dx", tag), B * H * W * cin * 2)
+        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(dz), cout, 0, A.ptr(img), None, A.ptr(zero_shift), rdlib.ptr(residual), cin, 0, None, 0, 0, 0,
+                    None, A.ptr(out), cin, 0, B, H, W, cout, cin, 1, rdlib.RD_SCALE_FOLDED | rdlib.RD_ADD, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, cin), self.dt)
 
 
 BN_EPS = 1e-5 + 1e-10      # mxnext/complicate.py:26-45 (normalizer_factory(type="localbn"))

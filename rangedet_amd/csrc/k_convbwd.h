@@ -4,7 +4,9 @@
 //   relu_affine_bwd_kernel       dz = g * [y > 0] * s[c], one float32 product rounded once
 //   conv3_bwd_weight_kernel      dW[co][ci][tap] = sum over pixels of dz[pix][co] * x[pix + tap][ci] on the matrix cores, partial sums per
 //                                workgroup in the workspace;  bwd_weight_reduce_kernel adds them in index order
-//   head_out_bwd_kernel          the 1x1 output conv: dx (optionally times [x > 0] * s[c], the dz of the last tower conv), and the
+//   conv1_bwd_weight_kernel      the same for a 1x1 conv (the projection shortcut of a backbone BasicBlock): dW[co][ci], one tap, the flat
+//                                pixel axis;  bwd1_weight_reduce_kernel adds the partial images in index order
+//   head_out_bwd_kernel         the 1x1 output conv: dx (optionally times [x > 0] * s[c], the dz of the last tower conv), and the
 //                                partial sums of dw and dbias;  head_out_bwd_reduce_kernel adds them in index order
 // (The data gradient of a 3x3 conv is the forward launch on the transposed, flipped weight: rangedet_amd/backward.py.)
 // No atomics anywhere: every sum has a fixed order, two calls give the same bits.
@@ -165,6 +167,127 @@ __global__ __launch_bounds__(256) void bwd_weight_reduce_kernel(const float* __r
   for (int k = 1; k < S; ++k) sum += part[(long)k * n + idx];
   const int t = idx / (cout * cin), co = idx / cin % cout, ci = idx % cin;
   dW[((long)co * cin + ci) * 9 + t] = sum;
+}
+
+// ---- weight gradient of a 1x1 conv (the projection shortcut of a backbone BasicBlock, dla_backbone.py:34-51) --------------------------------
+// dW[co][ci] = sum over pixels of dz[pix][co] * x[pix][ci]: the one-tap form of the kernel above.  Without a tap there is no image edge, so
+// the pixel axis is the flat run of B H W pixels in tiles of BW_PT; a chunk is one tile, and the last one is clamped and zero-filled.  The
+// same register transpose into [channel][pixel] rows and the same fragment reads; no shifted x image, no ring: one x tile and one dz tile
+// in LDS, the next chunk's loads in flight during this chunk's MFMAs.
+// The kernel is a stream: (cin + cout) * 2 bytes per pixel against cin * cout * 2 multiply-adds, 64 to 128 per byte.  A workgroup
+// therefore owns ALL cout x cin outputs (at most sixteen 32 x 32 tiles, four per wave: 64 accumulator registers), so that every input byte
+// is read once, and the launch is split over the pixel axis only.  A partial image costs cout * cin * 4 bytes written and read again --
+// the bytes of four chunks at 128 x 128 -- so the library's own split gives a workgroup at least BW1_MIN_CHUNKS = 8 chunks (the partial
+// sums then move at most half of what the inputs do) and stops at BW_WG_TARGET workgroups, two per CU of a 256-CU part, the most that are
+// resident at once with 36 KB of LDS each.
+constexpr int BW1_MIN_CHUNKS = 8;
+
+inline long bw1_chunks(int B, int H, int W) { return ((long)B * H * W + BW_PT - 1) / BW_PT; }
+inline long bw1_split(int B, int H, int W, int split) {
+  const long n = bw1_chunks(B, H, W), own = (n + BW1_MIN_CHUNKS - 1) / BW1_MIN_CHUNKS;
+  const long cap = split > 0 ? split : (own < BW_WG_TARGET ? own : BW_WG_TARGET);
+  return n < cap ? n : cap;
+}
+inline size_t bw1_weight_ws_bytes(int B, int H, int W, int cin, int cout, int split) {
+  return (size_t)bw1_split(B, H, W, split) * cout * cin * sizeof(float);
+}
+
+struct BwdW1Args {
+  const unsigned short *x, *dz;
+  int x_cs, x_co, dz_cs, dz_co;
+  long npix, nchunks;
+  float* part;   // [S][cout][cin]
+};
+
+// eight pixels p0 .. p0 + 7 of the flat pixel run, 8 channels each; addresses past the end are clamped and the values zeroed
+__device__ __forceinline__ void bw1_load(const unsigned short* __restrict__ base, int cs, long p0, long npix, Slot16 (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const long p = p0 + j, pc = p < npix ? p : npix - 1;
+    const Slot16 t = *(const Slot16*)(base + pc * cs);
+    v[j] = p == pc ? t : Slot16{0u, 0u, 0u, 0u};
+  }
+}
+
+// grid (S), 256 threads.  Waves: CIN 128 -> wave w owns input channels [32 w, 32 w + 32) and every 32-row block of the output channels;
+// CIN 64 -> wave w owns input channels 32 (w & 1) .. and the output half w >> 1.
+template <int DT, int CIN, int COUT>
+__global__ __launch_bounds__(256) void conv1_bwd_weight_kernel(BwdW1Args a) {
+  constexpr int WN = CIN / 32 < 4 ? CIN / 32 : 4, WM = 4 / WN, MT = COUT / 32 / WM;
+  constexpr int NXU = (BW_PT / 8) * (CIN / 8), NZU = (BW_PT / 8) * (COUT / 8);   // load units of an x tile and of a dz tile
+  static_assert(NXU + NZU <= 256, "one load unit per thread");
+  __shared__ __attribute__((aligned(16))) unsigned short Tx[CIN][BW_RS];
+  __shared__ __attribute__((aligned(16))) unsigned short Tz[COUT][BW_RS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int S = gridDim.x, s = blockIdx.x;
+  const int wn = wave % WN, wm = wave / WN;
+  const bool is_x = tid < NXU, is_z = tid >= NXU && tid < NXU + NZU;
+  const int u = is_x ? tid : tid - NXU;            // unit: pixel group u % 8, channel group u / 8
+  const int pg = u & 7, cg = u >> 3;
+  f32x16 acc[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+  const unsigned short* xb = a.x + a.x_co + 8 * cg;
+  const unsigned short* zb = a.dz + a.dz_co + 8 * cg;
+  const long c_lo = s * a.nchunks / S, c_hi = (s + 1) * a.nchunks / S;
+  Slot16 v[8];
+  auto load = [&](long ch) {
+    const long p0 = ch * BW_PT + 8 * pg;
+    if (is_x) bw1_load(xb, a.x_cs, p0, a.npix, v);
+    else if (is_z) bw1_load(zb, a.dz_cs, p0, a.npix, v);
+  };
+  if (c_lo < c_hi) load(c_lo);
+  for (long ch = c_lo; ch < c_hi; ++ch) {
+    if (is_x) bw_store_t(Tx, 8 * cg, pg, v);
+    else if (is_z) bw_store_t(Tz, 8 * cg, pg, v);
+    __syncthreads();
+    if (ch + 1 < c_hi) load(ch + 1);   // the next chunk's loads fly during this chunk's MFMAs
+    const int r = lane & 31, k8 = 8 * (lane >> 5);
+#pragma unroll
+    for (int ks = 0; ks < BW_PT / 16; ++ks) {
+      const s16x8 bf = *(const s16x8*)&Tx[32 * wn + r][16 * ks + k8];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const s16x8 af = *(const s16x8*)&Tz[32 * (wm * MT + i) + r][16 * ks + k8];
+        acc[i] = H16<DT>::mfma(af, bf, acc[i]);
+      }
+    }
+    __syncthreads();
+  }
+  // D[m][n]: column n = lane & 31 (input channel), row m = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (output channel)
+  const int ci = 32 * wn + (lane & 31);
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int rg = 0; rg < 16; ++rg) {
+      const int co = 32 * (wm * MT + i) + (rg & 3) + 8 * (rg >> 2) + 4 * (lane >> 5);
+      a.part[((long)s * COUT + co) * CIN + ci] = acc[i][rg];
+    }
+}
+
+// dW (cout, cin) = the S partial images added in index order.  There are only cout * cin threads (16 to 64 workgroups) and the sum of a
+// thread is one dependent chain, so the launch runs at the latency of its loads: they are issued BW1_RED_BATCH at a time (independent,
+// clamped to the last image and the value dropped) and then added one by one in index order.
+constexpr int BW1_RED_BATCH = 16;
+__global__ __launch_bounds__(256) void bwd1_weight_reduce_kernel(const float* __restrict__ part, int S, int n, float* __restrict__ dW) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  float sum = 0.f;
+  for (int k0 = 0; k0 < S; k0 += BW1_RED_BATCH) {
+    float v[BW1_RED_BATCH];
+#pragma unroll
+    for (int j = 0; j < BW1_RED_BATCH; ++j) {
+      const int k = k0 + j < S ? k0 + j : S - 1;
+      v[j] = part[(long)k * n + idx];
+    }
+#pragma unroll
+    for (int j = 0; j < BW1_RED_BATCH; ++j)
+      if (k0 + j < S) sum += v[j];
+  }
+  dW[idx] = sum;
 }
 
 // ---- dz = g * [y > 0] * s[c] -----------------------------------------------------------------------------------------------------------

@@ -44,6 +44,21 @@
 //   dbeta = sum gy;  dgamma: acc = fmaf(gy, zh, acc)                       per thread in pixel order, lanes in lane order, tree over k
 //   c1 = dbeta / N;  c2 = dgamma / N;  gr = gamma * rstd
 //   dz = round16(gr * fmaf(-zh, c2, gy - c1))                              one rounding to the activation type
+//
+// ---- residual form: the second BatchNorm of a backbone BasicBlock (dla_backbone.py:31-45: conv2 -> BN -> + shortcut -> ReLU) ----------------
+// r is the shortcut in the activation type: the block input (identity, ar = br = NULL) or the output zs of the 1x1 projection conv, whose own
+// BatchNorm is folded into ar, br (rd_bn_stats and rd_bn_fold on zs).  The same work split, the same clamped loads, one more tensor each.
+//   affine_add_relu_kernel                               t = fmaf(z, a, b);  u = ar ? fmaf(r, ar, br) : r;  v = t + u (a rounding of its own)
+//                                                        y = round16(relu ? max(v, 0) : v)
+//   bn_add_bwd_partial_kernel + bn_add_bwd_final_kernel  one sweep over g, z, r: the mask is [t + u > 0] with t, u, and their sum formed exactly as
+//                                                        above (y is not read);  gy = mask ? g : 0;  zh = (z - mean) * rstd
+//                                                        dbeta = sum gy;  dgamma: acc = fmaf(gy, zh, acc)
+//                                                        projection: zhr = (r - mean_r) * rstd_r;  dgamma_r: acc = fmaf(gy, zhr, acc);  dbeta_r = dbeta
+//                                                        (two or three partial sums per workgroup and channel, ws[(0, 1, 2) P + k][c], then nm_tree32)
+//   bn_add_bwd_dzdr_kernel                               c1 = dbeta / N;  c2 = dgamma / N;  dz = round16(gamma * rstd * fmaf(-zh, c2, gy - c1))
+//                                                        identity:    dr = gy (its 16 bits are those of g, or +0)
+//                                                        projection:  c2r = dgamma_r / N;  dr = round16(gamma_r * rstd_r * fmaf(-zhr, c2r, gy - c1))
+//                                                        one launch reads g, z, r once more and writes both tensors
 #pragma once
 #include "rd_common.h"
 
@@ -356,6 +371,218 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(NmBwdArgs a) {
         fg[j] = gr[j] * fmaf(-zh, c2[j], gy - c1[j]);
       }
       if (q < hi) *(Slot16*)(ob + q * a.dz_cs) = slot_pack<DT>(fg);
+    }
+  }
+}
+
+// ---- residual form: y = round16(max(fmaf(z, a, b) + u, 0)), u = r or fmaf(r, ar, br) ------------------------------------------------------------
+struct NmAddArgs {
+  const unsigned short *z, *r;
+  int z_cs, z_co, r_cs, r_co;
+  const float *a, *b, *ar, *br;   // ar, br: both NULL for an identity shortcut
+  int relu;
+  unsigned short* y;
+  int y_cs, y_co, C;
+  long npix;
+};
+// the eight per-channel values of a slot; p == nullptr gives `dflt`
+__device__ __forceinline__ void nm_vec8(const float* __restrict__ p, int sl, float dflt, float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = p ? p[8 * sl + j] : dflt;
+}
+// v = fmaf(z, a, b) + u: what the forward rounds and the backward takes the sign of
+template <bool PROJ>
+__device__ __forceinline__ float nm_add_pre(float z, float r, float sa, float sb, float ra, float rb) {
+  _Pragma("clang fp contract(off)")
+  const float t = fmaf(z, sa, sb);
+  const float u = PROJ ? fmaf(r, ra, rb) : r;
+  return t + u;
+}
+
+template <int DT, bool PROJ>
+__global__ __launch_bounds__(256) void affine_add_relu_kernel(NmAddArgs a) {
+  _Pragma("clang fp contract(off)")
+  const int slots = a.C / 8, PL = 256 / slots, tid = threadIdx.x, sl = tid % slots, pl = tid / slots;
+  const long per = (long)PL * NM_UNROLL * NM_EW_ITERS, lo = blockIdx.x * per, hi = lo + per < a.npix ? lo + per : a.npix;
+  const unsigned short* zb = a.z + a.z_co + 8 * sl;
+  const unsigned short* rb = a.r + a.r_co + 8 * sl;
+  unsigned short* yb = a.y + a.y_co + 8 * sl;
+  float sa[8], sb[8], ra[8], rbv[8];
+  nm_vec8(a.a, sl, 0.f, sa);
+  nm_vec8(a.b, sl, 0.f, sb);
+  nm_vec8(PROJ ? a.ar : nullptr, sl, 0.f, ra);
+  nm_vec8(PROJ ? a.br : nullptr, sl, 0.f, rbv);
+  for (long q0 = lo + pl; q0 < hi; q0 += (long)NM_UNROLL * PL) {
+    Slot16 vz[NM_UNROLL], vr[NM_UNROLL];
+    nm_load(zb, a.z_cs, q0, PL, hi, vz);
+    nm_load(rb, a.r_cs, q0, PL, hi, vr);
+#pragma unroll
+    for (int u = 0; u < NM_UNROLL; ++u) {
+      const long q = q0 + (long)u * PL;
+      float fz[8], fr[8];
+      slot_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vr[u], fr);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = nm_add_pre<PROJ>(fz[j], fr[j], sa[j], sb[j], ra[j], rbv[j]);
+        fz[j] = a.relu ? fmaxf(v, 0.f) : v;
+      }
+      if (q < hi) *(Slot16*)(yb + q * a.y_cs) = slot_pack<DT>(fz);
+    }
+  }
+}
+
+struct NmAddBwdArgs {
+  const unsigned short *g, *z, *r;
+  int g_cs, g_co, z_cs, z_co, r_cs, r_co;
+  const float *a, *b, *mean, *rstd, *gamma;
+  const float *ar, *br, *mean_r, *rstd_r, *gamma_r;   // all NULL for an identity shortcut
+  unsigned short *dz, *dr;
+  int dz_cs, dz_co, dr_cs, dr_co, C, P;
+  long npix;
+  float* part;                             // [2 or 3][P][C]: sum gy, sum gy zh, sum gy zhr
+  const float *dbeta, *dgamma, *dgamma_r;  // the dz / dr launch reads the sums the final launch wrote
+};
+
+template <int DT, bool PROJ>
+__global__ __launch_bounds__(256) void bn_add_bwd_partial_kernel(NmAddBwdArgs a) {
+  _Pragma("clang fp contract(off)")
+  __shared__ float red[PROJ ? 3 : 2][2048];
+  const int C = a.C, slots = C / 8, PL = 256 / slots, tid = threadIdx.x, sl = tid % slots, pl = tid / slots;
+  const long k = blockIdx.x, lo = k * a.npix / a.P, hi = (k + 1) * a.npix / a.P;
+  const unsigned short* gb = a.g + a.g_co + 8 * sl;
+  const unsigned short* zb = a.z + a.z_co + 8 * sl;
+  const unsigned short* rb = a.r + a.r_co + 8 * sl;
+  float sa[8], sb[8], mu[8], rs[8], ra[8], rbv[8], mur[8], rsr[8], sg[8], sz[8], sr[8];
+  nm_vec8(a.a, sl, 0.f, sa);
+  nm_vec8(a.b, sl, 0.f, sb);
+  nm_vec8(a.mean, sl, 0.f, mu);
+  nm_vec8(a.rstd, sl, 0.f, rs);
+  nm_vec8(PROJ ? a.ar : nullptr, sl, 0.f, ra);
+  nm_vec8(PROJ ? a.br : nullptr, sl, 0.f, rbv);
+  nm_vec8(PROJ ? a.mean_r : nullptr, sl, 0.f, mur);
+  nm_vec8(PROJ ? a.rstd_r : nullptr, sl, 0.f, rsr);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sg[j] = sz[j] = sr[j] = 0.f;
+  for (long q0 = lo + pl; q0 < hi; q0 += (long)NM_UNROLL * PL) {
+    Slot16 vg[NM_UNROLL], vz[NM_UNROLL], vr[NM_UNROLL];
+    nm_load(gb, a.g_cs, q0, PL, hi, vg);
+    nm_load(zb, a.z_cs, q0, PL, hi, vz);
+    nm_load(rb, a.r_cs, q0, PL, hi, vr);
+#pragma unroll
+    for (int u = 0; u < NM_UNROLL; ++u) {
+      const bool ok = q0 + (long)u * PL < hi;
+      float fg[8], fz[8], fr[8];
+      slot_unpack<DT>(vg[u], fg);
+      slot_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vr[u], fr);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool on = ok && nm_add_pre<PROJ>(fz[j], fr[j], sa[j], sb[j], ra[j], rbv[j]) > 0.f;
+        const float gy = on ? fg[j] : 0.f;
+        const float zh = (fz[j] - mu[j]) * rs[j];
+        sg[j] += gy;
+        sz[j] = fmaf(gy, zh, sz[j]);
+        if (PROJ) {
+          const float zhr = (fr[j] - mur[j]) * rsr[j];
+          sr[j] = fmaf(gy, zhr, sr[j]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[0][pl * C + 8 * sl + j] = sg[j];
+    red[1][pl * C + 8 * sl + j] = sz[j];
+    if (PROJ) red[2][pl * C + 8 * sl + j] = sr[j];
+  }
+  __syncthreads();
+  if (tid < C) {
+    a.part[k * C + tid] = lane_sum(red[0], PL, C, tid);
+    a.part[((long)a.P + k) * C + tid] = lane_sum(red[1], PL, C, tid);
+    if (PROJ) a.part[(2L * a.P + k) * C + tid] = lane_sum(red[2], PL, C, tid);
+  }
+}
+
+// grid (C / 8, 2 or 3): blockIdx.y 0 -> dbeta (and dbeta_r, the same value), 1 -> dgamma, 2 -> dgamma_r
+__global__ __launch_bounds__(256) void bn_add_bwd_final_kernel(const float* __restrict__ part, int P, int C, float* __restrict__ dbeta,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta_r,
+                                                               float* __restrict__ dgamma_r) {
+  _Pragma("clang fp contract(off)")
+  __shared__ float red[NM_KL][8];
+  const int cl = threadIdx.x & 7, kl = threadIdx.x >> 3, c = 8 * blockIdx.x + cl;
+  const float* p = part + (long)blockIdx.y * P * C + c;
+  float acc = 0.f;
+  for (long k = kl; k < P; k += NM_KL) acc += p[k * C];
+  const float s = nm_tree32(acc, red, kl, cl);
+  if (kl != 0) return;
+  if (blockIdx.y == 0) {
+    dbeta[c] = s;
+    if (dbeta_r) dbeta_r[c] = s;
+  } else {
+    (blockIdx.y == 1 ? dgamma : dgamma_r)[c] = s;
+  }
+}
+
+template <int DT, bool PROJ>
+__global__ __launch_bounds__(256) void bn_add_bwd_dzdr_kernel(NmAddBwdArgs a) {
+  _Pragma("clang fp contract(off)")
+  const int slots = a.C / 8, PL = 256 / slots, tid = threadIdx.x, sl = tid % slots, pl = tid / slots;
+  const long per = (long)PL * NM_UNROLL * NM_EW_ITERS, lo = blockIdx.x * per, hi = lo + per < a.npix ? lo + per : a.npix;
+  const unsigned short* gb = a.g + a.g_co + 8 * sl;
+  const unsigned short* zb = a.z + a.z_co + 8 * sl;
+  const unsigned short* rb = a.r + a.r_co + 8 * sl;
+  unsigned short* ozb = a.dz + a.dz_co + 8 * sl;
+  unsigned short* orb = a.dr + a.dr_co + 8 * sl;
+  const float N = (float)a.npix;
+  float sa[8], sb[8], mu[8], rs[8], ra[8], rbv[8], mur[8], rsr[8], gr[8], grr[8], c1[8], c2[8], c2r[8];
+  nm_vec8(a.a, sl, 0.f, sa);
+  nm_vec8(a.b, sl, 0.f, sb);
+  nm_vec8(a.mean, sl, 0.f, mu);
+  nm_vec8(a.rstd, sl, 0.f, rs);
+  nm_vec8(PROJ ? a.ar : nullptr, sl, 0.f, ra);
+  nm_vec8(PROJ ? a.br : nullptr, sl, 0.f, rbv);
+  nm_vec8(PROJ ? a.mean_r : nullptr, sl, 0.f, mur);
+  nm_vec8(PROJ ? a.rstd_r : nullptr, sl, 0.f, rsr);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = 8 * sl + j;
+    gr[j] = a.gamma[c] * rs[j];
+    c1[j] = a.dbeta[c] / N;
+    c2[j] = a.dgamma[c] / N;
+    grr[j] = PROJ ? a.gamma_r[c] * rsr[j] : 0.f;
+    c2r[j] = PROJ ? a.dgamma_r[c] / N : 0.f;
+  }
+  for (long q0 = lo + pl; q0 < hi; q0 += (long)NM_UNROLL * PL) {
+    Slot16 vg[NM_UNROLL], vz[NM_UNROLL], vr[NM_UNROLL];
+    nm_load(gb, a.g_cs, q0, PL, hi, vg);
+    nm_load(zb, a.z_cs, q0, PL, hi, vz);
+    nm_load(rb, a.r_cs, q0, PL, hi, vr);
+#pragma unroll
+    for (int u = 0; u < NM_UNROLL; ++u) {
+      const long q = q0 + (long)u * PL;
+      float fg[8], fz[8], fr[8];
+      slot_unpack<DT>(vg[u], fg);
+      slot_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vr[u], fr);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool on = nm_add_pre<PROJ>(fz[j], fr[j], sa[j], sb[j], ra[j], rbv[j]) > 0.f;
+        const float gy = on ? fg[j] : 0.f;
+        const float zh = (fz[j] - mu[j]) * rs[j];
+        const float d = gy - c1[j];
+        fz[j] = gr[j] * fmaf(-zh, c2[j], d);
+        if (PROJ) {
+          const float zhr = (fr[j] - mur[j]) * rsr[j];
+          fr[j] = grr[j] * fmaf(-zhr, c2r[j], d);
+        } else {
+          fr[j] = gy;
+        }
+      }
+      if (q < hi) {
+        *(Slot16*)(ozb + q * a.dz_cs) = slot_pack<DT>(fz);
+        *(Slot16*)(orb + q * a.dr_cs) = slot_pack<DT>(fr);
+      }
     }
   }
 }

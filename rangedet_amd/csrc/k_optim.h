@@ -31,6 +31,9 @@
 // followed by RD_CONV_TAIL zero bytes, which the launch writes too.  No padding channels exist at these sizes, so every weight element
 // lands at exactly one position of each image; a thread gathers its eight values (the weight was written by the launch before, it is in
 // L2) and stores one 16-byte slot.  Rounding is round-to-nearest-even, what h16_from_f32 does on the host.
+// A (cout, cin, 1, 1) weight of the same channel counts (the projection shortcut of a backbone BasicBlock) has the same two images with
+// ONE tap instead of nine -- what rd_pack_conv_weight_host(w, cout, cin, 1, 1, dtype) writes for the weight and for its transpose: the
+// table is unchanged, the tap count of an entry is n / (cout cin), 9 or 1.
 #pragma once
 #include "k_conv.h"
 
@@ -59,7 +62,9 @@ struct SgdChunk { int tensor, chunk; };
 struct SgdPackChunk { int tensor, image, run, pad; };   // image 0: forward, 1: data gradient
 static_assert(sizeof(SgdHeader) == 64 && sizeof(SgdEntry) % 8 == 0, "table layout");
 
-inline long sgd_image_slots(int cout, int cin) { return (long)(9 * cout * cin * 2 + RD_CONV_TAIL) / 16; }
+inline long sgd_image_slots(int cout, int cin, int ntaps = 9) { return (long)(ntaps * cout * cin * 2 + RD_CONV_TAIL) / 16; }
+// taps of an entry that names images: 9 (n = 9 cout cin), 1 (n = cout cin), else 0
+__host__ __device__ inline int sgd_ntaps(long n, int cout, int cin) { return n == 9L * cout * cin ? 9 : n == (long)cout * cin ? 1 : 0; }
 inline bool sgd_pack_shape_ok(int cout, int cin) { return (cout == 64 || cout == 128) && (cin == 64 || cin == 128); }
 
 // the checks of one tensor; -> RD_OK or the code, the message left in the error buffer
@@ -72,14 +77,14 @@ inline int sgd_check_tensor(const rd_sgd_tensor_t& t, int i) {
     RD_REQUIRE(sgd_pack_shape_ok(t.cout, t.cin), RD_ESHAPE,
                "sgd_table: tensor %d: images of a (%d, %d, 3, 3) weight -- 64 or 128 channels on either side, stride 1 (not the <= 16-channel "
                "body form, the stride-2 pair view, M16 images or the 72-channel concat)", i, t.cout, t.cin);
-    RD_REQUIRE(t.n == 9L * t.cout * t.cin, RD_ESHAPE, "sgd_table: tensor %d: n %ld is not 9 x %d x %d", i, t.n, t.cout, t.cin);
+    RD_REQUIRE(sgd_ntaps(t.n, t.cout, t.cin) != 0, RD_ESHAPE, "sgd_table: tensor %d: n %ld is not 9 x %d x %d (3x3) or 1 x that (1x1)", i, t.n, t.cout, t.cin);
   }
   RD_REQUIRE(!t.fold_scale || t.pack_fwd, RD_EINVAL, "sgd_table: tensor %d: a fold scale without a forward image", i);
   return RD_OK;
 }
 inline long sgd_tensor_chunks(const rd_sgd_tensor_t& t) { return (t.n + SGD_CHUNK - 1) / SGD_CHUNK; }
 inline long sgd_tensor_pack_chunks(const rd_sgd_tensor_t& t) {
-  const long per = (sgd_image_slots(t.cout, t.cin) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
+  const long per = (sgd_image_slots(t.cout, t.cin, sgd_ntaps(t.n, t.cout, t.cin)) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
   return (t.pack_fwd ? per : 0) + (t.pack_bwd ? per : 0);
 }
 inline size_t sgd_table_size(long nt, long n_chunks, long n_pack) {
@@ -104,7 +109,7 @@ inline void sgd_table_build(const rd_sgd_tensor_t* t, int nt, int dtype, long n_
     e[i].lr_mult = t[i].lr_mult; e[i].wd_mult = t[i].wd_mult; e[i].cout = t[i].cout; e[i].cin = t[i].cin;
     e[i].fwd = (unsigned short*)t[i].pack_fwd; e[i].bwd = (unsigned short*)t[i].pack_bwd; e[i].fold = t[i].fold_scale;
     for (long k = 0; k < sgd_tensor_chunks(t[i]); ++k) *c++ = SgdChunk{i, (int)k};
-    const long per = (sgd_image_slots(t[i].cout, t[i].cin) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
+    const long per = (sgd_image_slots(t[i].cout, t[i].cin, sgd_ntaps(t[i].n, t[i].cout, t[i].cin)) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
     for (int im = 0; im < 2; ++im)
       if (im == 0 ? t[i].pack_fwd : t[i].pack_bwd)
         for (long k = 0; k < per; ++k) *p++ = SgdPackChunk{i, im, (int)k, 0};
@@ -154,30 +159,31 @@ __global__ __launch_bounds__(256) void sgd_mom_kernel(const unsigned char* __res
   }
 }
 
-// one 16-byte slot of one image of a (cout, cin, 3, 3) float32 weight; image 0: forward (fold may be NULL), 1: data gradient
+// one 16-byte slot of one image of a (cout, cin, 3, 3) (nt 9) or (cout, cin, 1, 1) (nt 1) float32 weight; image 0: forward (fold may be
+// NULL), 1: data gradient
 template <int DT>
 __device__ __forceinline__ void sgd_pack_slot(const float* __restrict__ w, const float* __restrict__ fold, int cout, int cin, int image,
-                                              long slot, unsigned short* __restrict__ out) {
+                                              long slot, unsigned short* __restrict__ out, int nt = 9) {
   _Pragma("clang fp contract(off)")
-  const long body = 9L * cout * cin / 8;
+  const long body = (long)nt * cout * cin / 8;
   if (slot >= body + (long)(RD_CONV_TAIL / 16)) return;
   Slot16 o = {0u, 0u, 0u, 0u};
   if (slot < body) {
     const int ncb = (image ? cin : cout) / 32, lg = ncb >> 1;   // ncb is 2 or 4: its logarithm
     const int s = (int)slot, lane = s & 63, cb = (s >> 6) & (ncb - 1);
     const int u = s >> (6 + lg);                             // (c * 9 + t) * 2 + ks
-    const int ks = u & 1, t = (u >> 1) % 9, c = (u >> 1) / 9;
+    const int ks = u & 1, t = (u >> 1) % nt, c = (u >> 1) / nt;
     const int r = 32 * cb + conv_row_perm(lane & 31), q0 = 32 * c + 16 * ks + 8 * (lane >> 5);
     float f[8];
     if (image == 0) {
       const float sc = fold ? fold[r] : 1.f;
-      const float* src = w + ((long)r * cin + q0) * 9 + t;
+      const float* src = w + ((long)r * cin + q0) * nt + t;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = sc * src[9 * j];
+      for (int j = 0; j < 8; ++j) f[j] = sc * src[nt * j];
     } else {
-      const float* src = w + ((long)q0 * cin + r) * 9 + (8 - t);
+      const float* src = w + ((long)q0 * cin + r) * nt + (nt - 1 - t);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = src[(long)9 * cin * j];
+      for (int j = 0; j < 8; ++j) f[j] = src[(long)nt * cin * j];
     }
     o = slot_pack<DT>(f);
   }
@@ -189,7 +195,8 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const unsigned char* __re
   const SgdHeader* h = (const SgdHeader*)table;
   const SgdPackChunk pk = ((const SgdPackChunk*)(table + h->off_pack))[blockIdx.x];
   const SgdEntry e = ((const SgdEntry*)(table + h->off_entries))[pk.tensor];
-  sgd_pack_slot<DT>(e.w, e.fold, e.cout, e.cin, pk.image, (long)pk.run * SGD_PACK_SLOTS + threadIdx.x, pk.image ? e.bwd : e.fwd);
+  sgd_pack_slot<DT>(e.w, e.fold, e.cout, e.cin, pk.image, (long)pk.run * SGD_PACK_SLOTS + threadIdx.x, pk.image ? e.bwd : e.fwd,
+                    sgd_ntaps(e.n, e.cout, e.cin));
 }
 
 // the single-tensor form: grid = ceil(slots / 256)

@@ -1153,6 +1153,39 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   return check_launch("conv3x3_bwd_weight");
 }
 
+size_t rd_conv1x1_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split) {
+  return bhw_ok(B, H, W) && split >= 0 && bw_weight_shape_ok(cin, cout) ? bw1_weight_ws_bytes(B, H, W, cin, cout, split) : 0;
+}
+int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                          int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "conv1x1_bwd_weight: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "conv1x1_bwd_weight: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "conv1x1_bwd_weight: split %d (0: the library's choice)", split);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "conv1x1_bwd_weight: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(bw_weight_shape_ok(cin, cout), RD_ESHAPE, "conv1x1_bwd_weight: cin %d, cout %d (each 64 or 128; stride 1)", cin, cout);
+  RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
+             "conv1x1_bwd_weight: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dz) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)dW) % 4 == 0, RD_EINVAL,
+             "conv1x1_bwd_weight: x and dz must be 16-byte aligned, dW and the workspace 4-byte aligned");
+  const size_t need = bw1_weight_ws_bytes(B, H, W, cin, cout, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "conv1x1_bwd_weight: workspace %zu < %zu bytes", ws_bytes, need);
+  const long S = bw1_split(B, H, W, split);
+  RD_REQUIRE(S <= 0x7fffffffL, RD_ESHAPE, "conv1x1_bwd_weight: split %ld", S);
+  BwdW1Args a;
+  a.x = (const unsigned short*)x; a.dz = (const unsigned short*)dz;
+  a.x_cs = x_cstride; a.x_co = x_coff; a.dz_cs = dz_cstride; a.dz_co = dz_coff;
+  a.npix = (long)B * H * W; a.nchunks = bw1_chunks(B, H, W);
+  a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S);
+  if (cin == 128 && cout == 128) RD_LAUNCH_H16(dtype, (conv1_bwd_weight_kernel<DT, 128, 128>), grid, dim3(256), st, a);
+  else if (cin == 128) RD_LAUNCH_H16(dtype, (conv1_bwd_weight_kernel<DT, 128, 64>), grid, dim3(256), st, a);
+  else if (cout == 128) RD_LAUNCH_H16(dtype, (conv1_bwd_weight_kernel<DT, 64, 128>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv1_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
+  hipLaunchKernelGGL(bwd1_weight_reduce_kernel, dim3((cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout * cin, dW);
+  return check_launch("conv1x1_bwd_weight");
+}
+
 size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout) {
   return bhw_ok(B, H, W) && (cin == 64 || cin == 128) && nout >= 1 && nout <= 8 ? hob_ws_bytes((long)B * H * W, cin) : 0;
 }
@@ -1277,6 +1310,75 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 8, 2), dim3(256), 0, st, (const float*)ws, f.P, C, dbeta, dgamma);
   RD_LAUNCH_H16(dtype, (bn_bwd_dz_kernel<DT>), dim3((unsigned)nb), dim3(256), st, f);
   return check_launch("bn_relu_bwd");
+}
+
+// the residual form: the second BatchNorm of a backbone BasicBlock, + shortcut, ReLU
+int rd_affine_add_relu(const void* z, int z_cstride, int z_coff, const float* a, const float* b, const void* r, int r_cstride, int r_coff,
+                       const float* ar, const float* br, int relu, void* y, int y_cstride, int y_coff, int B, int H, int W, int C, int dtype,
+                       void* stream) {
+  RD_REQUIRE(z && a && b && r && y, RD_EINVAL, "affine_add_relu: null pointer");
+  RD_REQUIRE(!ar == !br, RD_EINVAL, "affine_add_relu: ar and br go together (both NULL: an identity shortcut)");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "affine_add_relu: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "affine_add_relu: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "affine_add_relu: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(r_cstride, r_coff, C) && nhwc16_ok(y_cstride, y_coff, C), RD_ESHAPE,
+             "affine_add_relu: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)z | (uintptr_t)r | (uintptr_t)y) % 16 == 0 && ((uintptr_t)a | (uintptr_t)b | (uintptr_t)ar | (uintptr_t)br) % 4 == 0,
+             RD_EINVAL, "affine_add_relu: the tensors must be 16-byte aligned, the float vectors 4-byte aligned");
+  NmAddArgs f;
+  f.z = (const unsigned short*)z; f.z_cs = z_cstride; f.z_co = z_coff; f.r = (const unsigned short*)r; f.r_cs = r_cstride; f.r_co = r_coff;
+  f.a = a; f.b = b; f.ar = ar; f.br = br; f.relu = relu ? 1 : 0;
+  f.y = (unsigned short*)y; f.y_cs = y_cstride; f.y_co = y_coff; f.C = C; f.npix = (long)B * H * W;
+  const long nb = nm_ew_blocks(f.npix, C);
+  RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "affine_add_relu: %ld pixels", f.npix);
+  hipStream_t st = (hipStream_t)stream;
+  if (ar) RD_LAUNCH_H16(dtype, (affine_add_relu_kernel<DT, true>), dim3((unsigned)nb), dim3(256), st, f);
+  else RD_LAUNCH_H16(dtype, (affine_add_relu_kernel<DT, false>), dim3((unsigned)nb), dim3(256), st, f);
+  return check_launch("affine_add_relu");
+}
+
+size_t rd_bn_add_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split, int projection) {
+  return bhw_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * (projection ? 3 : 2) * C * sizeof(float) : 0;
+}
+int rd_bn_add_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int z_cstride, int z_coff, const void* r, int r_cstride,
+                       int r_coff, const float* a, const float* b, const float* mean, const float* rstd, const float* gamma, const float* ar,
+                       const float* br, const float* mean_r, const float* rstd_r, const float* gamma_r, void* dz, int dz_cstride, int dz_coff,
+                       void* dr, int dr_cstride, int dr_coff, float* dgamma, float* dbeta, float* dgamma_r, float* dbeta_r, int B, int H, int W,
+                       int C, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(g && z && r && a && b && mean && rstd && gamma && dz && dr && dgamma && dbeta && ws, RD_EINVAL, "bn_add_relu_bwd: null pointer");
+  const bool proj = ar != nullptr;
+  RD_REQUIRE(proj ? (br && mean_r && rstd_r && gamma_r && dgamma_r && dbeta_r) : (!br && !mean_r && !rstd_r && !gamma_r && !dgamma_r && !dbeta_r),
+             RD_EINVAL, "bn_add_relu_bwd: ar, br, mean_r, rstd_r, gamma_r, dgamma_r and dbeta_r go together (all NULL: an identity shortcut)");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "bn_add_relu_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "bn_add_relu_bwd: split %d (0: the library's choice)", split);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "bn_add_relu_bwd: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "bn_add_relu_bwd: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, C) && nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(r_cstride, r_coff, C) &&
+             nhwc16_ok(dz_cstride, dz_coff, C) && nhwc16_ok(dr_cstride, dr_coff, C), RD_ESHAPE,
+             "bn_add_relu_bwd: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)g | (uintptr_t)z | (uintptr_t)r | (uintptr_t)dz | (uintptr_t)dr) % 16 == 0 &&
+             ((uintptr_t)a | (uintptr_t)b | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)ar | (uintptr_t)br | (uintptr_t)mean_r |
+              (uintptr_t)rstd_r | (uintptr_t)gamma_r | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)dgamma_r | (uintptr_t)dbeta_r | (uintptr_t)ws) % 4 == 0,
+             RD_EINVAL, "bn_add_relu_bwd: the tensors must be 16-byte aligned, the float buffers 4-byte aligned");
+  const size_t need = rd_bn_add_relu_bwd_workspace_bytes(B, H, W, C, split, proj);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "bn_add_relu_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+  NmAddBwdArgs f;
+  f.g = (const unsigned short*)g; f.z = (const unsigned short*)z; f.r = (const unsigned short*)r;
+  f.g_cs = g_cstride; f.g_co = g_coff; f.z_cs = z_cstride; f.z_co = z_coff; f.r_cs = r_cstride; f.r_co = r_coff;
+  f.a = a; f.b = b; f.mean = mean; f.rstd = rstd; f.gamma = gamma;
+  f.ar = ar; f.br = br; f.mean_r = mean_r; f.rstd_r = rstd_r; f.gamma_r = gamma_r;
+  f.dz = (unsigned short*)dz; f.dz_cs = dz_cstride; f.dz_co = dz_coff; f.dr = (unsigned short*)dr; f.dr_cs = dr_cstride; f.dr_co = dr_coff; f.C = C;
+  f.npix = (long)B * H * W; f.P = (int)nm_parts(f.npix, split); f.part = (float*)ws;
+  f.dbeta = dbeta; f.dgamma = dgamma; f.dgamma_r = dgamma_r;
+  const long nb = nm_ew_blocks(f.npix, C);
+  RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "bn_add_relu_bwd: %ld pixels", f.npix);
+  hipStream_t st = (hipStream_t)stream;
+  if (proj) RD_LAUNCH_H16(dtype, (bn_add_bwd_partial_kernel<DT, true>), dim3(f.P), dim3(256), st, f);
+  else RD_LAUNCH_H16(dtype, (bn_add_bwd_partial_kernel<DT, false>), dim3(f.P), dim3(256), st, f);
+  hipLaunchKernelGGL(bn_add_bwd_final_kernel, dim3(C / 8, proj ? 3 : 2), dim3(256), 0, st, (const float*)ws, f.P, C, dbeta, dgamma, dbeta_r, dgamma_r);
+  if (proj) RD_LAUNCH_H16(dtype, (bn_add_bwd_dzdr_kernel<DT, true>), dim3((unsigned)nb), dim3(256), st, f);
+  else RD_LAUNCH_H16(dtype, (bn_add_bwd_dzdr_kernel<DT, false>), dim3((unsigned)nb), dim3(256), st, f);
+  return check_launch("bn_add_relu_bwd");
 }
 
 // ---- SGD with momentum over a table of tensors, and the conv weight images re-packed on the device (k_optim.h) ----------------------

@@ -139,6 +139,9 @@ SIGNATURES = {
     "rd_conv3x3_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rd_conv3x3_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_conv1x1_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rd_conv1x1_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_size_t, c_void_p]),
     "rd_head_out_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rd_head_out_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
@@ -151,6 +154,12 @@ SIGNATURES = {
     "rd_bn_relu_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rd_bn_relu_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_void_p,
                                c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_affine_add_relu": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rd_bn_add_relu_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rd_bn_add_relu_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 10
+                           + [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 4
+                           + [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rd_sgd_table_bytes": (c_size_t, [c_void_p, c_int]),
     "rd_sgd_table_host": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "rd_sgd_mom_update": (c_int, [c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p]),

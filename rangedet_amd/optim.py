@@ -120,9 +120,9 @@ class SGD:
         self._key = self._host = self._dev = None
 
     def add(self, name, weight, grad, pack=None, lr_mult=1.0, wd_mult=None):
-        """weight, grad: float32 device tensors of one shape, 16-byte aligned.  pack, for a (cout, cin, 3, 3) conv weight with 64 or 128
-        channels on either side: dict(fwd=, bwd=, fold_scale=, dtype=) -- the device buffers of the forward image (with an optional device
-        vector of cout scales folded in) and of the data-gradient image, either may be None; both are rewritten by every step.  wd_mult
+        """weight, grad: float32 device tensors of one shape, 16-byte aligned.  pack, for a (cout, cin, 3, 3) or (cout, cin, 1, 1) conv weight
+        with 64 or 128 channels on either side: dict(fwd=, bwd=, fold_scale=, dtype=) -- the device buffers of the forward image (with an optional
+        device vector of cout scales folded in) and of the data-gradient image, either may be None; both are rewritten by every step.  wd_mult
         None: 1 for names ending in _weight or _gamma, else 0.  Registering a name again replaces its buffers and keeps its momentum."""
         _check_f32(weight, name)
         _check_f32(grad, name + " gradient")
@@ -133,10 +133,10 @@ class SGD:
                  wd_mult=default_wd_mult(name) if wd_mult is None else float(wd_mult), cout=0, cin=0, fwd=None, bwd=None, fold=None)
         if pack is not None:
             shp = e["shape"]
-            if len(shp) != 4 or shp[2:] != (3, 3) or shp[0] not in (64, 128) or shp[1] not in (64, 128):
-                raise NotImplementedError("%s: weight images of shape %r -- a (cout, cin, 3, 3) conv weight with 64 or 128 channels on either "
-                                          "side (not the <= 16-channel body form, the stride-2 pair view, M16 images or the 72-channel concat)"
-                                          % (name, shp))
+            if len(shp) != 4 or shp[2:] not in ((3, 3), (1, 1)) or shp[0] not in (64, 128) or shp[1] not in (64, 128):
+                raise NotImplementedError("%s: weight images of shape %r -- a (cout, cin, 3, 3) or (cout, cin, 1, 1) conv weight with 64 or 128 "
+                                          "channels on either side (not the <= 16-channel body form, the stride-2 pair view, M16 images or the "
+                                          "72-channel concat)" % (name, shp))
             dt = pack.get("dtype", rdlib.RD_BF16)
             if dt not in rdlib.H16 or self._dtype not in (None, dt):
                 raise ValueError("%s: image type %r; one 16-bit type (RD_BF16 / RD_F16) per optimizer" % (name, dt))
