@@ -524,8 +524,10 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * Every reduction is split over workgroups whose partial sums go to the caller's workspace and are added in index order by a second
  * launch: no atomics, two calls on the same inputs give the same bits, and the bits do not depend on the device's CU count.  All launches
  * go on `stream`, nothing synchronises, the contents of ws on entry do not matter.  Every check precedes the first launch.
- * Training-mode normalisation (batch statistics, the gradients of gamma and beta) is the next section.  Not here: the concat conv,
- * strided and transposed convs.
+ * Training-mode normalisation (batch statistics, the gradients of gamma and beta) is the next section.  The stride-(1,2) 3x3 conv of a
+ * down-sampling BasicBlock: weight gradient rd_conv3x3_bwd_weight_ex, data gradient rd_deconv2d_bn_act_all on the weight read as a (3,4)
+ * transposed-conv weight with a zero fourth column; its strided 1x1 shortcut runs the 1x1 calls on the pixel-pair view (channel stride
+ * 2 cin).  Not here: the concat conv, the backward of the network's own transposed convs.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -546,6 +548,15 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
  * split x cout x cin floats at most; split, the absence of atomics and the determinism are those of rd_conv3x3_bwd_weight.  The data
  * gradient of the 1x1 conv is rd_conv2d_bn_act with kh = kw = 1 on the transposed weight packed by rd_pack_conv_weight_host. */
 size_t rd_conv1x1_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split);
+/* rd_conv3x3_bwd_weight with a stride: stride_w 1 gives its bytes with its partial count and workspace size; stride_w 2 is the weight
+ * gradient of a 3x3 stride-(1,2) pad-1 conv (conv2 of a down-sampling BasicBlock), x (B, H, Win) and dz (B, H, Win / 2):
+ *   dW[co,ci,ky,kx] = sum_{b,h,wo} dz[b,h,wo,co] x[b,h+ky-1,2wo+kx-1,ci]      (x zero outside the image)
+ * Win odd with stride_w 2, stride_w outside {1, 2}, cin or cout outside {64, 128}: RD_ESHAPE.  The same kernel: a workgroup owns a tap
+ * column and 64 output channels and reads x at twice the pixel stride; chunks, the split and the workspace (split x 9 x cout x cin floats
+ * at most) are counted on the dz grid (B, 16-row strips, 64-pixel tiles of Win / stride_w).  No atomics, two calls give the same bytes. */
+size_t rd_conv3x3_bwd_weight_ex_workspace_bytes(int B, int H, int Win, int cin, int cout, int stride_w, int split);
+int rd_conv3x3_bwd_weight_ex(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                             int Win, int cin, int cout, int stride_w, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
                           int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 /* Backward of rd_head_out.  d_out: float32 at d_out[b*out_batch_stride + (n_off + h*W + w)*nout + o], exactly as rd_head_out writes `out`
@@ -659,7 +670,15 @@ int rd_bn_add_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, 
  * refused with RD_ESHAPE.  A (cout, cin, 1, 1) weight of the same channel counts (n = cout cin: the tap count of an entry follows from n)
  * may name images too: pack_fwd, byte for byte what rd_pack_conv_weight_host(w, cout, cin, 1, 1, dtype) writes (rd_conv_packed_bytes(1, cin,
  * cout, dtype) bytes, zero tail included), and pack_bwd, the same packer on the transposed (cin, cout) weight: what rd_conv2d_bn_act with
- * kh = kw = 1 reads for the conv and for its data gradient.  A step is two launches at most; the library allocates nothing and never synchronises; every check precedes
+ * kh = kw = 1 reads for the conv and for its data gradient.
+ * stride_w == 2 on a (C, C, 3, 3) weight, C 64 or 128 (conv2 of a down-sampling BasicBlock; cin != cout or a 1x1 weight: RD_ESHAPE) names
+ * the images of the strided launches instead: pack_fwd, byte for byte what rd_pack_conv3x3_ex_host(w, fold_scale, C, C, 2, C, dtype) writes
+ * (the pixel-pair view in the body form rd_conv3x3_bn_act_ex takes at stride_w 2; rd_conv3x3_ex_packed_bytes(C, C, 2, C) bytes), and
+ * pack_bwd, the two phase images rd_pack_deconv_weight_folded_host(w' , NULL, C, C, 3, 4, 2, 1, phase, dtype, .) writes for w' = w read as
+ * (Cin, Cout, 3, 3) with a zero column appended at kx = 3, phase 1 starting rd_conv_packed_bytes(6, C, C, dtype) bytes after phase 0: what
+ * rd_deconv2d_bn_act_all reads as the data gradient of the strided conv.  Zero fill and zero tails are written too.  stride_w is the last
+ * field: a caller that fills the eleven fields before it and zeroes the rest gets the table it got before.
+ * A step is two launches at most; the library allocates nothing and never synchronises; every check precedes
  * the first launch. */
 typedef struct {
   void* weight;             /* float32 device buffers of n elements */
@@ -671,6 +690,7 @@ typedef struct {
   void* pack_fwd;           /* device images, or NULL */
   void* pack_bwd;
   const float* fold_scale;  /* device, cout values, or NULL; needs pack_fwd */
+  int stride_w;             /* 0 or 1: the images above; 2: the images of a (C, C, 3, 3) stride-(1,2) conv, see above */
 } rd_sgd_tensor_t;
 size_t rd_sgd_table_bytes(const rd_sgd_tensor_t* tensors, int nt);   /* 0: refused (rd_last_error_string says why) */
 int rd_sgd_table_host(const rd_sgd_tensor_t* tensors, int nt, int dtype, void* out);   /* dtype: that of the images */

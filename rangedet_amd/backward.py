@@ -36,7 +36,9 @@ its master, its gradient buffer and its images: rangedet_amd.optim.SGD.attach(to
 forward() and backward() run on the new weights -- no host copy, no new tower.  A tower that is never attached behaves as before.
 
 TowerOps also holds the steps of a backbone BasicBlock (the residual batch norm forward and backward, the 1x1 conv, its weight gradient, the
-data gradient with a residual added in its epilogue): rangedet_amd.backbone_train builds BasicBlockTrain and ResStageTrain from them.
+data gradient with a residual added in its epilogue) and those of its stride-(1,2) form (the strided 3x3 conv, its weight and data
+gradients, the 1x1 calls on the pixel-pair view): rangedet_amd.backbone_train builds BasicBlockTrain, DownBlockTrain and ResStageTrain
+from them.
 """
 import numpy as np
 
@@ -83,10 +85,11 @@ class TowerOps:
         self.A = alloc
         self._bufs = {}
 
-    def buf(self, key, nbytes):
+    def buf(self, key, nbytes, zero=False):
+        """zero: zeroed when it is first made (a buffer of which only a part is ever written keeps zeros elsewhere)"""
         k = (key, nbytes)
         if k not in self._bufs:
-            self._bufs[k] = self.A.alloc(nbytes)
+            self._bufs[k] = self.A.alloc(nbytes, zero=True) if zero else self.A.alloc(nbytes)
         return self._bufs[k]
 
     def pack_data_grad(self, w_oihw):
@@ -110,15 +113,24 @@ class TowerOps:
         img, zero_shift, cin = packed
         return self.conv3x3(dz, img, zero_shift, _check16(dz, "dz")[3], cin, rdlib.RD_SCALE_FOLDED, ("dx", tag))
 
-    def weight_grad(self, x, dz, tag=0, split=0):
-        """x (B, H, W, cin), dz (B, H, W, cout) -> dW (cout, cin, 3, 3) float32"""
+    def weight_grad(self, x, dz, tag=0, split=0, stride_w=1):
+        """x (B, H, W, cin), dz (B, H, W / stride_w, cout) -> dW (cout, cin, 3, 3) float32; stride_w 2: the stride-(1,2) conv
+        (rd_conv3x3_bwd_weight_ex), W even"""
         A, L = self.A, self.L
         B, H, W, cin = _check16(x, "x")
-        if _check16(dz, "dz")[:3] != (B, H, W):
-            raise ValueError("weight_grad: x %r and dz %r differ in B, H or W" % (tuple(x.shape), tuple(dz.shape)))
+        if stride_w not in (1, 2) or W % stride_w:
+            raise NotImplementedError("weight_grad: stride_w %r with W %d -- 1, or 2 with an even width" % (stride_w, W))
+        if _check16(dz, "dz")[:3] != (B, H, W // stride_w):
+            raise ValueError("weight_grad: x %r and dz %r differ in B, H or W / %d" % (tuple(x.shape), tuple(dz.shape), stride_w))
         cout = int(dz.shape[3])
         if cin not in (64, 128) or cout not in (64, 128):
             raise NotImplementedError("weight_grad: %d -> %d channels; the kernel runs 64 or 128 on either side" % (cin, cout))
+        if stride_w == 2:
+            nws = L.raw("rd_conv3x3_bwd_weight_ex_workspace_bytes")(B, H, W, cin, cout, 2, split)
+            ws, out = self.buf(("bww_ws", 0), nws), self.buf(("dW", tag), cout * cin * 36)
+            L.call("rd_conv3x3_bwd_weight_ex", rdlib.ptr(x), cin, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, W, cin, cout, 2, split, self.dt,
+                   A.ptr(ws), nws, _stream(A))
+            return A.view_f32(out, (cout, cin, 3, 3))
         nws = L.raw("rd_conv3x3_bwd_weight_workspace_bytes")(B, H, W, cin, cout, split)
         ws, out = self.buf(("bww_ws", 0), nws), self.buf(("dW", tag), cout * cin * 36)
         L.call("rd_conv3x3_bwd_weight", rdlib.ptr(x), cin, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, W, cin, cout, split, self.dt, A.ptr(ws),
@@ -243,30 +255,92 @@ class TowerOps:
         w = np.ascontiguousarray(np.asarray(w_oi, np.float32).reshape(w_oi.shape[0], -1))
         return self.A.upload(self.L.pack_conv_weight(w.reshape(w.shape + (1, 1)), self.dt))
 
-    def conv1x1(self, x, image, cin, cout, key):
+    def conv1x1(self, x, image, cin, cout, key, pair=None):
         """x (B, H, W, cin) -> conv1x1(x, W) rounded to the activation type, in the buffer `key`; image = pack_conv1x1(W).  With the image of
-        the transposed weight this is the 1x1 conv's data gradient."""
+        the transposed weight this is the 1x1 conv's data gradient.  The stride-(1,2) 1x1 conv runs the same launch on the pixel-pair view,
+        a row of W pixels read as W / 2 pixels of twice the channel stride whose first cin (cout) channels are the even pixel:
+          pair='in'    x (B, H, W, cin), W even -> (B, H, W / 2, cout): the conv of the even pixels, the strided forward
+          pair='out'   x (B, H, Wo, cin) -> (B, H, 2 Wo, cout): the result on the even pixels, +0 on the odd ones (the buffer is zeroed when
+                       it is made and its odd pixels are never written), the strided conv's data gradient"""
         A = self.A
         B, H, W = _check16(x, "x")[:3]
-        out = self.buf(key, B * H * W * cout * 2)
-        self.L.call("rd_conv2d_bn_act", rdlib.ptr(x), cin, 0, A.ptr(image), None, None, None, 0, 0, A.ptr(out), cout, 0, B, H, W, cin, cout, 1, 1,
-                    1, 0, self.dt, _stream(A))
-        return _view16(A, out, (B, H, W, cout), self.dt)
+        if pair not in (None, "in", "out") or (pair == "in" and W % 2):
+            raise NotImplementedError("conv1x1: pair %r with W %d -- None, 'in' with an even width, or 'out'" % (pair, W))
+        Wl, Wout = (W // 2, W // 2) if pair == "in" else (W, 2 * W if pair == "out" else W)
+        out = self.buf(key, B * H * Wout * cout * 2, zero=pair == "out")
+        self.L.call("rd_conv2d_bn_act", rdlib.ptr(x), cin * (2 if pair == "in" else 1), 0, A.ptr(image), None, None, None, 0, 0, A.ptr(out),
+                    cout * (2 if pair == "out" else 1), 0, B, H, Wl, cin, cout, 1, 1, 1, 0, self.dt, _stream(A))
+        return _view16(A, out, (B, H, Wout, cout), self.dt)
 
-    def weight_grad1x1(self, x, dz, tag=0, split=0):
-        """x (B, H, W, cin), dz (B, H, W, cout) -> dW (cout, cin, 1, 1) float32"""
+    def weight_grad1x1(self, x, dz, tag=0, split=0, pair=False):
+        """x (B, H, W, cin), dz (B, H, W, cout) -> dW (cout, cin, 1, 1) float32.  pair: the stride-(1,2) conv -- dz (B, H, W / 2, cout) against
+        the even pixels of x, read through the pixel-pair view (channel stride 2 cin; W even keeps the flat pixel axis whole)"""
         A, L = self.A, self.L
         B, H, W, cin = _check16(x, "x")
-        if _check16(dz, "dz")[:3] != (B, H, W):
-            raise ValueError("weight_grad1x1: x %r and dz %r differ in B, H or W" % (tuple(x.shape), tuple(dz.shape)))
+        if pair and W % 2:
+            raise NotImplementedError("weight_grad1x1: the pixel-pair view of a row of %d pixels (an even width)" % W)
+        Wl = W // 2 if pair else W
+        if _check16(dz, "dz")[:3] != (B, H, Wl):
+            raise ValueError("weight_grad1x1: x %r and dz %r differ in B, H or W%s" % (tuple(x.shape), tuple(dz.shape), " / 2" if pair else ""))
         cout = int(dz.shape[3])
         if cin not in (64, 128) or cout not in (64, 128):
             raise NotImplementedError("weight_grad1x1: %d -> %d channels; the kernel runs 64 or 128 on either side" % (cin, cout))
-        nws = L.raw("rd_conv1x1_bwd_weight_workspace_bytes")(B, H, W, cin, cout, split)
+        nws = L.raw("rd_conv1x1_bwd_weight_workspace_bytes")(B, H, Wl, cin, cout, split)
         ws, out = self.buf(("bww_ws", 0), nws), self.buf(("dW1", tag), cout * cin * 4)
-        L.call("rd_conv1x1_bwd_weight", rdlib.ptr(x), cin, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, W, cin, cout, split, self.dt, A.ptr(ws),
-               nws, _stream(A))
+        L.call("rd_conv1x1_bwd_weight", rdlib.ptr(x), cin * (2 if pair else 1), 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, Wl, cin, cout, split,
+               self.dt, A.ptr(ws), nws, _stream(A))
         return A.view_f32(out, (cout, cin, 1, 1))
+
+    # ---- the stride-(1,2) 3x3 conv of a down-sampling BasicBlock (C -> C, C 64 or 128) -----------------------------------------------------
+    def pack_unscaled_s2(self, w_oihw):
+        """(image, zero shift, ones) of the strided conv: rd_pack_conv3x3_ex_host on the pixel-pair view.  The packer writes the body form a
+        RD_SCALE_FOLDED launch reads only when it is given a fold scale, so it gets a vector of ones (1.0f * w is w); the same vector on
+        the device is the entry's fold_scale, with which an optimizer step re-packs that form"""
+        w = np.asarray(w_oihw, np.float32)
+        C = w.shape[0]
+        if w.shape != (C, C, 3, 3) or C not in (64, 128):
+            raise NotImplementedError("pack_unscaled_s2: a (C, C, 3, 3) weight with C 64 or 128, got %r" % (w.shape,))
+        ones = np.ones(C, np.float32)
+        return self.A.upload(self.L.pack_conv3x3_ex(w, 2, C, fold_scale=ones, dtype=self.dt)), self.A.upload(np.zeros(C, np.float32)), self.A.upload(ones)
+
+    def conv_unscaled_s2(self, x, packed, C, tag=0):
+        """z = conv3x3 stride (1,2) of x (B, H, W, C), W even -> (B, H, W / 2, C) rounded to the activation type; packed = pack_unscaled_s2(W)"""
+        A = self.A
+        B, H, W, cx = _check16(x, "x")
+        if W % 2 or cx != C:
+            raise NotImplementedError("conv_unscaled_s2: x %r -- an even width and %d channels" % (tuple(x.shape), C))
+        out = self.buf(("z", tag), B * H * (W // 2) * C * 2)
+        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), C, 0, A.ptr(packed[0]), None, A.ptr(packed[1]), None, 0, 0, None, 0, 0, 0, None,
+                    A.ptr(out), C, 0, B, H, W, C, C, 2, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W // 2, C), self.dt)
+
+    def pack_data_grad_s2(self, w_oihw):
+        """the images of the strided conv's data gradient: it is the transposed conv with kernel (3,4), stride (1,2), pad (1,1) whose weight
+        is W (cout, cin, 3, 3) read as (Cin, Cout, KH, KW) with a zero column at kx = 3 -- no flip, no axis swap; both convs map
+        w = 2 wo - 1 + kx.  -> (the two phase images one after the other, zero shift, cin, bytes of a phase)"""
+        w = np.asarray(w_oihw, np.float32)
+        cout, cin = w.shape[:2]
+        wd = np.zeros((cout, cin, 3, 4), np.float32)
+        wd[..., :3] = w
+        if not self.L.raw("rd_deconv2d_all_phases_ok")(3, 4, 2, 1, cin, self.dt):
+            raise NotImplementedError("pack_data_grad_s2: %d input channels -- the all-phases transposed conv launch does not take them" % cin)
+        ph = [self.L.pack_deconv_weight(wd, 2, 1, p, self.dt) for p in (0, 1)]
+        return self.A.upload(np.concatenate(ph)), self.A.upload(np.zeros(cin, np.float32)), cin, int(ph[0].nbytes)
+
+    def data_grad_s2(self, dz, packed, residual=None, tag=0):
+        """dz (B, H, Wo, cout) -> the input gradient (B, H, 2 Wo, cin) of the strided conv; packed = pack_data_grad_s2(W).  residual
+        (B, H, 2 Wo, cin): added in the launch's epilogue, one float32 add and one rounding, as data_grad_add does"""
+        A = self.A
+        img, zero_shift, cin, phase_bytes = packed
+        B, H, Wo, cout = _check16(dz, "dz")
+        if residual is not None and _check16(residual, "residual") != (B, H, 2 * Wo, cin):
+            raise ValueError("data_grad_s2: residual %r, the input gradient is %r" % (tuple(residual.shape), (B, H, 2 * Wo, cin)))
+        out = self.buf(("dx", tag), B * H * 2 * Wo * cin * 2)
+        flags = rdlib.RD_SCALE_FOLDED | (rdlib.RD_ADD if residual is not None else 0)
+        self.L.call("rd_deconv2d_bn_act_all", rdlib.ptr(dz), cout, 0, A.ptr(img), phase_bytes, A.ptr(zero_shift),
+                    None if residual is None else rdlib.ptr(residual), cin, 0, A.ptr(out), cin, 0, B, H, Wo, cout, cin, 3, 4, 2, 1, flags, self.dt,
+                    _stream(A))
+        return _view16(A, out, (B, H, 2 * Wo, cin), self.dt)
 
     def data_grad_add(self, dz, packed, residual, tag=0):
         """data_grad with `residual` (B, H, W, cin) added in the launch's epilogue: one float32 add, one rounding (RD_ADD, no ReLU)"""

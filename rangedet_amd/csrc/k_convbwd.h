@@ -3,7 +3,8 @@
 // bias; float32 weight gradients as under multi_precision, tools/train.py:358-360).
 //   relu_affine_bwd_kernel       dz = g * [y > 0] * s[c], one float32 product rounded once
 //   conv3_bwd_weight_kernel      dW[co][ci][tap] = sum over pixels of dz[pix][co] * x[pix + tap][ci] on the matrix cores, partial sums per
-//                                workgroup in the workspace;  bwd_weight_reduce_kernel adds them in index order
+//                                workgroup in the workspace;  bwd_weight_reduce_kernel adds them in index order.  SW = 2: the stride-(1,2)
+//                                conv of a down-sampling BasicBlock, dz at half width against x[2 pix + tap]
 //   conv1_bwd_weight_kernel      the same for a 1x1 conv (the projection shortcut of a backbone BasicBlock): dW[co][ci], one tap, the flat
 //                                pixel axis;  bwd1_weight_reduce_kernel adds the partial images in index order
 //   head_out_bwd_kernel         the 1x1 output conv: dx (optionally times [x > 0] * s[c], the dz of the last tower conv), and the
@@ -49,14 +50,15 @@ struct BwdWArgs {
   int B, H, W, nwt, nhs;
   long nchunks;
   float* part;   // [S][9][cout][cin]
+  int Wz;        // pixels of a dz row: W (stride 1) or W / 2 (stride (1,2)); tiles, strips and chunks are counted on the dz grid
 };
 
-// eight pixels p0 .. p0 + 7 of one image row, 8 channels each.  Every address is clamped into the row and the value dropped afterwards:
-// no branch around a load.
-__device__ __forceinline__ void bw_load(const unsigned short* __restrict__ row, bool row_ok, int cs, int p0, int W, Slot16 (&v)[8]) {
+// eight pixels p0, p0 + step, .. p0 + 7 step of one image row, 8 channels each.  Every address is clamped into the row and the value
+// dropped afterwards: no branch around a load.
+__device__ __forceinline__ void bw_load(const unsigned short* __restrict__ row, bool row_ok, int cs, int p0, int W, Slot16 (&v)[8], int step = 1) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int p = p0 + j, pc = p < 0 ? 0 : p >= W ? W - 1 : p;
+    const int p = p0 + step * j, pc = p < 0 ? 0 : p >= W ? W - 1 : p;
     const Slot16 t = *(const Slot16*)(row + (long)pc * cs);
     const bool ok = row_ok && p == pc;
     v[j] = ok ? t : Slot16{0u, 0u, 0u, 0u};
@@ -80,8 +82,14 @@ __device__ __forceinline__ void bw_store_t(unsigned short (*T)[BW_RS], int c0, i
 
 // grid (S, 3, COUT / 64), 256 threads.  Waves: CIN 128 -> wave w owns input channels [32 w, 32 w + 32) and both 32-row halves of the
 // 64 output channels; CIN 64 -> wave w owns input channels 32 (w & 1) .. and output half w >> 1.
-template <int DT, int CIN, int COUT>
+// SW 2: the stride-(1,2) conv (conv2 of a down-sampling BasicBlock).  dz has Wz = W / 2 pixels per row and the tile runs over them; the
+// x image of column dw holds x[2 p + dw] at column p (zeros outside the image), i.e. the same eight loads per thread at twice the pixel
+// stride.  In a dense image a pixel is one or two whole 128-byte lines, and a load instruction already reads one pixel per eight (or
+// sixteen) lanes, so every line fetched is used in full: column 0 reads the even pixels, columns -1 and +1 the odd ones, the pixels of
+// the other parity are never touched by that workgroup.  Everything behind the loads is unchanged.
+template <int DT, int CIN, int COUT, int SW = 1>
 __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
+  static_assert(SW == 1 || SW == 2, "stride (1,1) or (1,2)");
   constexpr int WN = CIN / 32 < 4 ? CIN / 32 : 4, WM = 4 / WN, MT = 2 / WM;
   constexpr int NXU = (BW_PT / 8) * (CIN / 8), NZU = (BW_PT / 8) * (BW_COB / 8);   // load units of an x row and of a dz row
   static_assert(NXU + NZU <= 256, "one load unit per thread");
@@ -107,11 +115,12 @@ __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
     const int h0 = hs * BW_RH, h1 = h0 + BW_RH < a.H ? h0 + BW_RH : a.H;
     const int p0 = wt * BW_PT + 8 * pg;
     const unsigned short* xb = a.x + (long)b * a.H * a.W * a.x_cs + a.x_co + 8 * cg;
-    const unsigned short* zb = a.dz + (long)b * a.H * a.W * a.dz_cs + a.dz_co + cob * BW_COB + 8 * cg;
+    const int Wz = SW == 1 ? a.W : a.Wz;
+    const unsigned short* zb = a.dz + (long)b * a.H * Wz * a.dz_cs + a.dz_co + cob * BW_COB + 8 * cg;
     Slot16 v[8];
     auto load_x = [&](int r) {      // x row r shifted by dw; rows outside the image are zeros
       const int rc = r < 0 ? 0 : r >= a.H ? a.H - 1 : r;
-      bw_load(xb + (long)rc * a.W * a.x_cs, r == rc, a.x_cs, p0 + dw, a.W, v);
+      bw_load(xb + (long)rc * a.W * a.x_cs, r == rc, a.x_cs, SW * p0 + dw, a.W, v, SW);
     };
     if (is_x) {
       load_x(h0 - 1);
@@ -120,7 +129,7 @@ __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
       bw_store_t(Tx[h0 % 3], 8 * cg, pg, v);
       load_x(h0 + 1);
     } else if (is_z) {
-      bw_load(zb + (long)h0 * a.W * a.dz_cs, true, a.dz_cs, p0, a.W, v);
+      bw_load(zb + (long)h0 * Wz * a.dz_cs, true, a.dz_cs, p0, Wz, v);
     }
     for (int h = h0; h < h1; ++h) {
       if (is_x) bw_store_t(Tx[(h + 1) % 3], 8 * cg, pg, v);
@@ -128,7 +137,7 @@ __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
       __syncthreads();
       if (h + 1 < h1) {             // the next row's loads fly during this row's MFMAs
         if (is_x) load_x(h + 2);
-        else if (is_z) bw_load(zb + (long)(h + 1) * a.W * a.dz_cs, true, a.dz_cs, p0, a.W, v);
+        else if (is_z) bw_load(zb + (long)(h + 1) * Wz * a.dz_cs, true, a.dz_cs, p0, Wz, v);
       }
       const int r = lane & 31, k8 = 8 * (lane >> 5);
 #pragma unroll

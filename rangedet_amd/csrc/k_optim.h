@@ -34,6 +34,17 @@
 // A (cout, cin, 1, 1) weight of the same channel counts (the projection shortcut of a backbone BasicBlock) has the same two images with
 // ONE tap instead of nine -- what rd_pack_conv_weight_host(w, cout, cin, 1, 1, dtype) writes for the weight and for its transpose: the
 // table is unchanged, the tap count of an entry is n / (cout cin), 9 or 1.
+// A (C, C, 3, 3) weight with stride_w == 2 (conv2 of a down-sampling BasicBlock, C = 64 or 128) has the images of the strided launches:
+//   forward          what rd_pack_conv3x3_ex_host(w, fold, C, C, 2, C) writes: the pixel-pair view (2 C view channels) in the body form
+//                    conv3_body_s2 selects -- per four 32-channel chunks the units [odd: 6 steps | even: 3 | even: 3 | odd: 6], one slab
+//                    [ks][cb][lane][8] per step in program order (pack_body_frag, BODY 1): 18 C^2 bytes of weights, then zeros up to the
+//                    24 C^2 + RD_CONV_TAIL bytes rd_conv3x3_ex_packed_bytes(C, C, 2, C) reports.  That packer chooses the body form only
+//                    when it is given a fold scale (the form a RD_SCALE_FOLDED launch reads); without one it writes the six-tap form
+//                    pack_taps_frag(6, 2 C, C), and so does the step -- pass a vector of ones to train an unscaled strided conv
+//   data gradient    the two phase images of the transposed conv (3,4) / stride 2 / pad 1 whose weight is w read as (Cin, Cout, KH, KW)
+//                    with a zero column kx = 3: pack_taps_frag(6, C, C) each with its own zero tail, phase 1 right after phase 0.  Phase 0
+//                    holds, per tap row, [zero | kx 1], phase 1 [kx 2 | kx 0]; tap rows in the order ky = 2, 1, 0.
+// The table's layout does not change: SgdPackChunk.image is 2 for the strided forward image and 3 / 4 for the two phases.
 #pragma once
 #include "k_conv.h"
 
@@ -59,13 +70,18 @@ struct SgdEntry {
   const float* fold;
 };
 struct SgdChunk { int tensor, chunk; };
-struct SgdPackChunk { int tensor, image, run, pad; };   // image 0: forward, 1: data gradient
+struct SgdPackChunk { int tensor, image, run, pad; };   // image 0: forward, 1: data gradient; stride 2: 2 forward, 3 / 4 phase 0 / 1
 static_assert(sizeof(SgdHeader) == 64 && sizeof(SgdEntry) % 8 == 0, "table layout");
 
 inline long sgd_image_slots(int cout, int cin, int ntaps = 9) { return (long)(ntaps * cout * cin * 2 + RD_CONV_TAIL) / 16; }
 // taps of an entry that names images: 9 (n = 9 cout cin), 1 (n = cout cin), else 0
 __host__ __device__ inline int sgd_ntaps(long n, int cout, int cin) { return n == 9L * cout * cin ? 9 : n == (long)cout * cin ? 1 : 0; }
 inline bool sgd_pack_shape_ok(int cout, int cin) { return (cout == 64 || cout == 128) && (cin == 64 || cin == 128); }
+// stride 2 (C -> C): slots of the forward image and of ONE phase image, zero fill and zero tails included
+__host__ __device__ inline long sgd_s2_fwd_slots(int C) { return (long)(24 * C * C + (int)RD_CONV_TAIL) / 16; }
+__host__ __device__ inline long sgd_s2_phase_slots(int C) { return (long)(12 * C * C + (int)RD_CONV_TAIL) / 16; }
+inline bool sgd_is_s2(const rd_sgd_tensor_t& t) { return t.stride_w == 2 && (t.pack_fwd || t.pack_bwd); }
+inline long sgd_runs(long slots) { return (slots + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS; }
 
 // the checks of one tensor; -> RD_OK or the code, the message left in the error buffer
 inline int sgd_check_tensor(const rd_sgd_tensor_t& t, int i) {
@@ -80,10 +96,15 @@ inline int sgd_check_tensor(const rd_sgd_tensor_t& t, int i) {
     RD_REQUIRE(sgd_ntaps(t.n, t.cout, t.cin) != 0, RD_ESHAPE, "sgd_table: tensor %d: n %ld is not 9 x %d x %d (3x3) or 1 x that (1x1)", i, t.n, t.cout, t.cin);
   }
   RD_REQUIRE(!t.fold_scale || t.pack_fwd, RD_EINVAL, "sgd_table: tensor %d: a fold scale without a forward image", i);
+  RD_REQUIRE(t.stride_w >= 0 && t.stride_w <= 2, RD_EINVAL, "sgd_table: tensor %d: stride_w %d (0 or 1: stride 1; 2: stride (1,2))", i, t.stride_w);
+  if (sgd_is_s2(t))
+    RD_REQUIRE(t.cin == t.cout && sgd_ntaps(t.n, t.cout, t.cin) == 9, RD_ESHAPE,
+               "sgd_table: tensor %d: stride_w 2 images of a (%d, %d) weight with n %ld -- a (C, C, 3, 3) weight, C 64 or 128", i, t.cout, t.cin, t.n);
   return RD_OK;
 }
 inline long sgd_tensor_chunks(const rd_sgd_tensor_t& t) { return (t.n + SGD_CHUNK - 1) / SGD_CHUNK; }
 inline long sgd_tensor_pack_chunks(const rd_sgd_tensor_t& t) {
+  if (sgd_is_s2(t)) return (t.pack_fwd ? sgd_runs(sgd_s2_fwd_slots(t.cout)) : 0) + (t.pack_bwd ? 2 * sgd_runs(sgd_s2_phase_slots(t.cout)) : 0);
   const long per = (sgd_image_slots(t.cout, t.cin, sgd_ntaps(t.n, t.cout, t.cin)) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
   return (t.pack_fwd ? per : 0) + (t.pack_bwd ? per : 0);
 }
@@ -109,6 +130,13 @@ inline void sgd_table_build(const rd_sgd_tensor_t* t, int nt, int dtype, long n_
     e[i].lr_mult = t[i].lr_mult; e[i].wd_mult = t[i].wd_mult; e[i].cout = t[i].cout; e[i].cin = t[i].cin;
     e[i].fwd = (unsigned short*)t[i].pack_fwd; e[i].bwd = (unsigned short*)t[i].pack_bwd; e[i].fold = t[i].fold_scale;
     for (long k = 0; k < sgd_tensor_chunks(t[i]); ++k) *c++ = SgdChunk{i, (int)k};
+    if (sgd_is_s2(t[i])) {
+      if (t[i].pack_fwd)
+        for (long k = 0; k < sgd_runs(sgd_s2_fwd_slots(t[i].cout)); ++k) *p++ = SgdPackChunk{i, 2, (int)k, 0};
+      for (int ph = 0; ph < 2 && t[i].pack_bwd; ++ph)
+        for (long k = 0; k < sgd_runs(sgd_s2_phase_slots(t[i].cout)); ++k) *p++ = SgdPackChunk{i, 3 + ph, (int)k, 0};
+      continue;
+    }
     const long per = (sgd_image_slots(t[i].cout, t[i].cin, sgd_ntaps(t[i].n, t[i].cout, t[i].cin)) + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS;
     for (int im = 0; im < 2; ++im)
       if (im == 0 ? t[i].pack_fwd : t[i].pack_bwd)
@@ -190,11 +218,64 @@ __device__ __forceinline__ void sgd_pack_slot(const float* __restrict__ w, const
   *(Slot16*)(out + 8 * slot) = o;
 }
 
+// one 16-byte slot of an image of a (C, C, 3, 3) weight with stride (1,2): image 2 the forward image (fold may be NULL), 3 / 4 the data
+// gradient's phase 0 / 1; `out` is the start of that image
+template <int DT>
+__device__ __forceinline__ void sgd_pack_slot_s2(const float* __restrict__ w, const float* __restrict__ fold, int C, int image, long slot,
+                                                 unsigned short* __restrict__ out) {
+  _Pragma("clang fp contract(off)")
+  const long total = image == 2 ? sgd_s2_fwd_slots(C) : sgd_s2_phase_slots(C);
+  // the host packer takes the body form only with a fold scale (conv3_body_s2: the launch form of folded weights); without one it
+  // writes the six-tap form pack_taps_frag(6, 2 C, C), which fills the image
+  const long body = image == 2 ? (long)(fold ? 18 : 24) * C * C / 16 : (long)12 * C * C / 16;
+  if (slot >= total) return;
+  Slot16 o = {0u, 0u, 0u, 0u};
+  if (slot < body) {
+    const int ncb = C / 32, s = (int)slot, lane = s & 63, cb = (s >> 6) % ncb, u = s / (64 * ncb);   // u = step * 2 + ks
+    const int ks = u & 1, step = u >> 1;
+    const int r = 32 * cb + conv_row_perm(lane & 31);
+    float f[8];
+    if (image == 2 && !fold) {
+      const int t = step % 6, c = step / 6, dh = t >> 1, c0 = 32 * c + 16 * ks + 8 * (lane >> 5);   // view tap (dh, dw2 = (t & 1) - 1)
+      const bool odd = c0 >= C, zero = !odd && !(t & 1);
+      const int kx = odd ? ((t & 1) ? 2 : 0) : 1;
+      const float* src = w + (((long)r * C + (c0 - (odd ? C : 0))) * 3 + dh) * 3 + kx;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = zero ? 0.f : 1.f * src[9 * q];
+    } else if (image == 2) {
+      // step -> (unit of the group of four, ordinal): units [6 | 3 | 3 | 6] steps on chunks [odd r2 | even r2 | even r2 + 1 | odd r2 + 1]
+      const int grp = step / 18, gs = step % 18, j = gs < 6 ? 0 : gs < 9 ? 1 : gs < 12 ? 2 : 3, so = gs - (j == 0 ? 0 : j == 1 ? 6 : j == 2 ? 9 : 12);
+      const int ne = C / 32, r2 = 2 * grp, chunk = j == 0 ? ne + r2 : j == 1 ? r2 : j == 2 ? r2 + 1 : ne + r2 + 1;
+      const bool odd = j == 0 || j == 3;
+      const int dh = odd ? so >> 1 : so, kx = odd ? ((so & 1) ? 2 : 0) : 1;     // odd pixel: view column -1 is kx 0, column 0 is kx 2
+      const int ci0 = 32 * chunk + 16 * ks + 8 * (lane >> 5) - (odd ? C : 0);
+      const float sc = fold ? fold[r] : 1.f;
+      const float* src = w + (((long)r * C + ci0) * 3 + dh) * 3 + kx;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = sc * src[9 * q];
+    } else {
+      const int t = step % 6, c = step / 6, ky = 2 - t / 2;
+      const int kx = image == 3 ? ((t & 1) ? 1 : 3) : ((t & 1) ? 0 : 2);         // kx 3: the appended zero column
+      const int q0 = 32 * c + 16 * ks + 8 * (lane >> 5);
+      const float* src = w + (((long)q0 * C + r) * 3 + ky) * 3 + (kx == 3 ? 0 : kx);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = kx == 3 ? 0.f : src[(long)9 * C * q];
+    }
+    o = slot_pack<DT>(f);
+  }
+  *(Slot16*)(out + 8 * slot) = o;
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const unsigned char* __restrict__ table) {
   const SgdHeader* h = (const SgdHeader*)table;
   const SgdPackChunk pk = ((const SgdPackChunk*)(table + h->off_pack))[blockIdx.x];
   const SgdEntry e = ((const SgdEntry*)(table + h->off_entries))[pk.tensor];
+  if (pk.image >= 2) {       // uniform over the workgroup
+    unsigned short* out = pk.image == 2 ? e.fwd : e.bwd + (pk.image - 3) * 8 * sgd_s2_phase_slots(e.cout);
+    sgd_pack_slot_s2<DT>(e.w, e.fold, e.cout, pk.image, (long)pk.run * SGD_PACK_SLOTS + threadIdx.x, out);
+    return;
+  }
   sgd_pack_slot<DT>(e.w, e.fold, e.cout, e.cin, pk.image, (long)pk.run * SGD_PACK_SLOTS + threadIdx.x, pk.image ? e.bwd : e.fwd,
                     sgd_ntaps(e.n, e.cout, e.cin));
 }

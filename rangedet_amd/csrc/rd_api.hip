@@ -1143,6 +1143,7 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   a.B = B; a.H = H; a.W = W; a.nwt = (W + BW_PT - 1) / BW_PT; a.nhs = (H + BW_RH - 1) / BW_RH;
   a.nchunks = bw_chunks(B, H, W);
   a.part = (float*)ws;
+  a.Wz = W;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)S, 3, cout / BW_COB);
   if (cin == 128 && cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 128>), grid, dim3(256), st, a);
@@ -1151,6 +1152,49 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
   hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
   return check_launch("conv3x3_bwd_weight");
+}
+// the same with a stride: stride_w 1 forwards to the entry above (its bytes, its partial count, its workspace); stride_w 2 is the weight
+// gradient of a 3x3 stride-(1,2) pad-1 conv, x (B, H, Win) against dz (B, H, Win / 2): chunks and the split are counted on the dz grid
+static bool bw_ex_shape_ok(int B, int H, int Win, int cin, int cout, int stride_w) {
+  return bhw_ok(B, H, Win) && bw_weight_shape_ok(cin, cout) && (stride_w == 1 || (stride_w == 2 && Win % 2 == 0));
+}
+size_t rd_conv3x3_bwd_weight_ex_workspace_bytes(int B, int H, int Win, int cin, int cout, int stride_w, int split) {
+  return split >= 0 && bw_ex_shape_ok(B, H, Win, cin, cout, stride_w) ? bw_weight_ws_bytes(B, H, Win / stride_w, cin, cout, split) : 0;
+}
+int rd_conv3x3_bwd_weight_ex(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                             int Win, int cin, int cout, int stride_w, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "conv3x3_bwd_weight_ex: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "conv3x3_bwd_weight_ex: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "conv3x3_bwd_weight_ex: split %d (0: the library's choice)", split);
+  RD_REQUIRE(stride_w == 1 || stride_w == 2, RD_ESHAPE, "conv3x3_bwd_weight_ex: stride_w %d (1 or 2)", stride_w);
+  RD_REQUIRE(bhw_ok(B, H, Win), RD_ESHAPE, "conv3x3_bwd_weight_ex: B %d, H %d, Win %d", B, H, Win);
+  RD_REQUIRE(Win % stride_w == 0, RD_ESHAPE, "conv3x3_bwd_weight_ex: Win %d with stride_w 2 (an even width)", Win);
+  RD_REQUIRE(bw_weight_shape_ok(cin, cout), RD_ESHAPE, "conv3x3_bwd_weight_ex: cin %d, cout %d (each 64 or 128; pad 1)", cin, cout);
+  RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
+             "conv3x3_bwd_weight_ex: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dz) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)dW) % 4 == 0, RD_EINVAL,
+             "conv3x3_bwd_weight_ex: x and dz must be 16-byte aligned, dW and the workspace 4-byte aligned");
+  const int Wo = Win / stride_w;
+  const size_t need = bw_weight_ws_bytes(B, H, Wo, cin, cout, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "conv3x3_bwd_weight_ex: workspace %zu < %zu bytes", ws_bytes, need);
+  const long S = bw_split(B, H, Wo, cout, split);
+  RD_REQUIRE(S <= 0x7fffffffL, RD_ESHAPE, "conv3x3_bwd_weight_ex: split %ld", S);
+  if (stride_w == 1)
+    return rd_conv3x3_bwd_weight(x, x_cstride, x_coff, dz, dz_cstride, dz_coff, dW, B, H, Win, cin, cout, split, dtype, ws, ws_bytes, stream);
+  BwdWArgs a;
+  a.x = (const unsigned short*)x; a.dz = (const unsigned short*)dz;
+  a.x_cs = x_cstride; a.x_co = x_coff; a.dz_cs = dz_cstride; a.dz_co = dz_coff;
+  a.B = B; a.H = H; a.W = Win; a.Wz = Wo; a.nwt = (Wo + BW_PT - 1) / BW_PT; a.nhs = (H + BW_RH - 1) / BW_RH;
+  a.nchunks = bw_chunks(B, H, Wo);
+  a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, 3, cout / BW_COB);
+  if (cin == 128 && cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 128, 2>), grid, dim3(256), st, a);
+  else if (cin == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 64, 2>), grid, dim3(256), st, a);
+  else if (cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128, 2>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64, 2>), grid, dim3(256), st, a);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
+  return check_launch("conv3x3_bwd_weight_ex");
 }
 
 size_t rd_conv1x1_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split) {

@@ -139,6 +139,9 @@ SIGNATURES = {
     "rd_conv3x3_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rd_conv3x3_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_conv3x3_bwd_weight_ex_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rd_conv3x3_bwd_weight_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rd_conv1x1_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rd_conv1x1_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_size_t, c_void_p]),
@@ -173,7 +176,8 @@ SIGNATURES = {
 class SgdTensor(ctypes.Structure):
     """rd_sgd_tensor_t (include/rangedet_hip.h): one tensor of an SGD step"""
     _fields_ = [("weight", c_void_p), ("grad", c_void_p), ("mom", c_void_p), ("n", c_long), ("lr_mult", c_float), ("wd_mult", c_float),
-                ("cout", c_int), ("cin", c_int), ("pack_fwd", c_void_p), ("pack_bwd", c_void_p), ("fold_scale", c_void_p)]
+                ("cout", c_int), ("cin", c_int), ("pack_fwd", c_void_p), ("pack_bwd", c_void_p), ("fold_scale", c_void_p),
+                ("stride_w", c_int)]
 
 
 class RangeDetError(RuntimeError):

@@ -122,7 +122,8 @@ class SGD:
     def add(self, name, weight, grad, pack=None, lr_mult=1.0, wd_mult=None):
         """weight, grad: float32 device tensors of one shape, 16-byte aligned.  pack, for a (cout, cin, 3, 3) or (cout, cin, 1, 1) conv weight
         with 64 or 128 channels on either side: dict(fwd=, bwd=, fold_scale=, dtype=) -- the device buffers of the forward image (with an optional
-        device vector of cout scales folded in) and of the data-gradient image, either may be None; both are rewritten by every step.  wd_mult
+        device vector of cout scales folded in) and of the data-gradient image, either may be None; both are rewritten by every step.  With
+        stride_w=2 in the dict (a (C, C, 3, 3) weight) they are the images of the stride-(1,2) launches (rd_sgd_tensor_t.stride_w).  wd_mult
         None: 1 for names ending in _weight or _gamma, else 0.  Registering a name again replaces its buffers and keeps its momentum."""
         _check_f32(weight, name)
         _check_f32(grad, name + " gradient")
@@ -130,7 +131,7 @@ class SGD:
         if n <= 0 or _numel(grad) != n:
             raise ValueError("%s: %d weight and %d gradient elements (equal, at least one)" % (name, n, _numel(grad)))
         e = dict(weight=weight, grad=grad, n=n, shape=tuple(int(v) for v in weight.shape), lr_mult=float(lr_mult),
-                 wd_mult=default_wd_mult(name) if wd_mult is None else float(wd_mult), cout=0, cin=0, fwd=None, bwd=None, fold=None)
+                 wd_mult=default_wd_mult(name) if wd_mult is None else float(wd_mult), cout=0, cin=0, fwd=None, bwd=None, fold=None, stride_w=0)
         if pack is not None:
             shp = e["shape"]
             if len(shp) != 4 or shp[2:] not in ((3, 3), (1, 1)) or shp[0] not in (64, 128) or shp[1] not in (64, 128):
@@ -140,7 +141,9 @@ class SGD:
             dt = pack.get("dtype", rdlib.RD_BF16)
             if dt not in rdlib.H16 or self._dtype not in (None, dt):
                 raise ValueError("%s: image type %r; one 16-bit type (RD_BF16 / RD_F16) per optimizer" % (name, dt))
-            e.update(cout=shp[0], cin=shp[1], fwd=pack.get("fwd"), bwd=pack.get("bwd"), fold=pack.get("fold_scale"))
+            e.update(cout=shp[0], cin=shp[1], fwd=pack.get("fwd"), bwd=pack.get("bwd"), fold=pack.get("fold_scale"), stride_w=int(pack.get("stride_w", 0)))
+            if e["stride_w"] not in (0, 1, 2) or (e["stride_w"] == 2 and (shp[2:] != (3, 3) or shp[0] != shp[1])):
+                raise NotImplementedError("%s: stride_w %r images of a %r weight -- 0 / 1, or 2 for a (C, C, 3, 3) weight" % (name, pack.get("stride_w"), shp))
             if e["fold"] is not None and e["fwd"] is None:
                 raise ValueError("%s: a fold scale without a forward image" % name)
         for k in ("weight", "grad", "fwd", "bwd"):
@@ -167,7 +170,7 @@ class SGD:
                      for e in self._entries.values())
 
     def _build(self, key):
-        ts = [rdlib.SgdTensor(p[0], p[1], p[2], e["n"], e["lr_mult"], e["wd_mult"], e["cout"], e["cin"], p[3], p[4], p[5])
+        ts = [rdlib.SgdTensor(p[0], p[1], p[2], e["n"], e["lr_mult"], e["wd_mult"], e["cout"], e["cin"], p[3], p[4], p[5], e["stride_w"])
               for e, p in zip(self._entries.values(), key)]
         self._host = self.L.sgd_table(ts, rdlib.RD_BF16 if self._dtype is None else self._dtype)
         self._dev = self.A.upload(self._host)
