@@ -527,7 +527,8 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * Training-mode normalisation (batch statistics, the gradients of gamma and beta) is the next section.  The stride-(1,2) 3x3 conv of a
  * down-sampling BasicBlock: weight gradient rd_conv3x3_bwd_weight_ex, data gradient rd_deconv2d_bn_act_all on the weight read as a (3,4)
  * transposed-conv weight with a zero fourth column; its strided 1x1 shortcut runs the 1x1 calls on the pixel-pair view (channel stride
- * 2 cin).  Not here: the concat conv, the backward of the network's own transposed convs.
+ * 2 cin).  The network's own transposed convs: rd_deconv_bwd_weight and the packers declared with it.  Not here: the concat conv, the
+ * Meta-Kernel.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -559,6 +560,36 @@ int rd_conv3x3_bwd_weight_ex(const void* x, int x_cstride, int x_coff, const voi
                              int Win, int cin, int cout, int stride_w, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
                           int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* The backward of the network's transposed convs (the `agg` stages of the DLA backbone: Deconvolution -> BatchNorm -> ReLU -> add(skip, .)).
+ * x (B, H, Win, cin), W (cin, cout, 3, kw) in MXNet's Deconvolution layout, stride (1, s), pad (1, p) with kw - 2 p == s, so Wout = s Win;
+ * dz is the gradient at the output, (B, H, s Win, cout).  The two forms (kw, s, p) = (4, 2, 1) and (8, 4, 2) at the channel pairs of the
+ * shipped configs -- (3,8): 128 -> 128 and 128 -> 64; (3,4): 128 -> 64 and 64 -> 64 -- anything else is RD_ESHAPE.
+ *   forward   z[b,hi-1+kh,s wi-p+kw,co] += x[b,hi,wi,ci] W[ci,co,kh,kw]                       rd_deconv2d_bn_act_all
+ *   dW[ci,co,kh,kw] = sum_{b,hi,wi} x[b,hi,wi,ci] dz[b,hi-1+kh,s wi-p+kw,co]                   rd_deconv_bwd_weight (dz zero outside the image)
+ *   dx[b,hi,wi,ci] = sum_{co,kh,kw} dz[b,hi-1+kh,s wi-p+kw,co] W[ci,co,kh,kw]                  rd_conv3x3_bn_act_ex on the s-pixel view
+ * rd_deconv_bwd_weight is the kernel of rd_conv3x3_bwd_weight_ex with the two tensors swapped: the deconv input is the narrow tensor and its
+ * channels the M axis, dz the wide one, read at pixel stride s with the column offsets kw - p.  A workgroup owns ONE tap column kw and 64
+ * input channels; its contract is that of rd_conv3x3_bwd_weight_ex in every respect: fp32 accumulation on the matrix cores over the pixel
+ * axis, per-workgroup partial sums in ws added in index order by a second launch, no atomics, two calls give the same bytes.  There are
+ * min(split or 512 / (kw cin / 64), chunks) partial sums with chunks = B ceil(H / 16) ceil(Win / 64) counted on the x grid, and the workspace
+ * holds that many x 3 kw x cin x cout floats.
+ * The data gradient: dense dz [H][s Win][cout] IS [H][Win][s cout] -- view channel e cout + co is output pixel s wv + e -- and
+ *   dx = conv3x3(view, Wv),  Wv[ci, e cout + co, kh, dwv + 1] = W[ci,co,kh, s dwv + e + p] where 0 <= s dwv + e + p < kw, else 0
+ * a stride-1 rd_conv3x3_bn_act_ex launch with cin = s cout, cout = cin, RD_SCALE_FOLDED, zero shift, no activation (RD_ADD with a residual adds
+ * another gradient of x in the epilogue).  rd_pack_deconv_data_grad_host writes its weight image: byte for byte what
+ * rd_pack_conv3x3_ex_host(Wv, NULL, cin, s cout, 1, s cout, dtype) writes, rd_conv3x3_ex_packed_bytes(s cout, cin, 1, s cout) bytes.  One
+ * third of Wv's (view channel block, tap column) pairs are structurally zero in both forms; the launch multiplies them all the same.
+ * rd_pack_deconv_dev: one launch on a device-resident float32 master.  data_grad == 0: the stride_w forward phase images, phase ph at
+ * ph * w_phase_bytes (a multiple of 16, at least rd_conv_packed_bytes(6, cin, cout, dtype)), each byte for byte what
+ * rd_pack_deconv_weight_folded_host(w, NULL, ..., ph, dtype, .) writes, zero tail included; data_grad != 0: the image above, byte for byte
+ * the host one (w_phase_bytes is not read). */
+size_t rd_deconv_bwd_weight_workspace_bytes(int B, int H, int Win, int cin, int cout, int kw, int stride_w, int pad_w, int split);
+int rd_deconv_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                         int Win, int cin, int cout, int kw, int stride_w, int pad_w, int split, int dtype, void* ws, size_t ws_bytes,
+                         void* stream);
+int rd_pack_deconv_data_grad_host(const float* w, int cin, int cout, int kw, int stride_w, int pad_w, int dtype, void* out);
+int rd_pack_deconv_dev(const float* w_dev, int cin, int cout, int kw, int stride_w, int pad_w, int data_grad, long w_phase_bytes, int dtype,
+                       void* out_dev, void* stream);
 /* Backward of rd_head_out.  d_out: float32 at d_out[b*out_batch_stride + (n_off + h*W + w)*nout + o], exactly as rd_head_out writes `out`
  * -- so rd_rpn_loss's flat d_logit / d_delta buffers are read in place.  x: the output conv's input (the post-ReLU output of the last
  * tower conv), w (nout, cin) float32.  nout 1..8, cin 64 or 128 (else RD_ESHAPE).
@@ -623,7 +654,14 @@ int rd_bn_relu_bwd(const void* g, int g_cstride, int g_coff, const void* z, int 
 int rd_affine_add_relu(const void* z, int z_cstride, int z_coff, const float* a, const float* b, const void* r, int r_cstride, int r_coff,
                        const float* ar, const float* br, int relu, void* y, int y_cstride, int y_coff, int B, int H, int W, int C, int dtype,
                        void* stream);
-/* Its backward, three launches like rd_bn_relu_bwd: ONE sweep over g, z and r gives the two (identity) or three (projection) partial sums
+/* The join of an aggregation stage (dla_backbone.py agg_stage: Deconvolution -> BatchNorm -> ReLU -> add(skip, .)): the ReLU BEFORE the add.
+ *   y = round(max(fmaf(z, a[c], b[c]), 0) + (float)r)      one fused multiply-add, one float32 add, one rounding
+ * max(t, 0) is t where t > 0 and +0 elsewhere.  r has its own channel stride and offset; y may be z.  C, alignment and the status codes are
+ * those of rd_affine_relu.  It needs no backward launch: the up-branch gradient is rd_bn_relu_bwd(g, z, ...), which recomputes the mask
+ * [fmaf(z, a, b) > 0] from z, and the skip gradient is g itself. */
+int rd_affine_relu_add(const void* z, int z_cstride, int z_coff, const float* a, const float* b, const void* r, int r_cstride, int r_coff,
+                       void* y, int y_cstride, int y_coff, int B, int H, int W, int C, int dtype, void* stream);
+/* The backward of rd_affine_add_relu, three launches like rd_bn_relu_bwd: ONE sweep over g, z and r gives the two (identity) or three (projection) partial sums
  * per channel, a fixed-tree launch adds them, one elementwise launch writes dz and dr together.  g = dL/dy; a, b, mean, rstd, gamma of the
  * main branch and, for a projection shortcut, ar, br, mean_r, rstd_r, gamma_r of the shortcut's BatchNorm -- these five and the outputs
  * dgamma_r, dbeta_r are all given or all NULL (else RD_EINVAL).

@@ -25,8 +25,10 @@ Everything runs on the allocator's current stream without a host synchronisation
 A block keeps float32 masters and both 16-bit images of each conv weight on the device, and optimizer_entries() lists every trainable
 parameter the way the towers do: rangedet_amd.optim.SGD.attach(block) registers them and the forward() after a step() runs on the new
 weights.  Refused with NotImplementedError: fewer than 64 input channels (res1_unit1), the Meta-Kernel unit, channel counts outside
-{64, 128}, an identity shortcut between different channel counts, a strided unit handed to BasicBlockTrain.  Still without a backward:
-the transposed convs, the level-0 concat conv and the Meta-Kernel unit.
+{64, 128}, an identity shortcut between different channel counts, a strided unit handed to BasicBlockTrain.
+AggStageTrain is a whole `agg` stage -- the transposed conv, its BatchNorm and ReLU, the add of the skip, then a ResStageTrain -- forward
+and backward (its docstring has the steps), so the gradient of the head levels reaches the `res` stages below.  Still without a backward:
+the level-0 concat conv and the Meta-Kernel unit.
 """
 import numpy as np
 
@@ -64,6 +66,26 @@ def conv1x1_data_grad(dz, w_oi, dtype=rdlib.RD_BF16, lib=None, alloc=None):
     o = _ops(dtype, lib, alloc)
     w = np.asarray(w_oi, np.float32).reshape(w_oi.shape[0], -1)
     return o.conv1x1(dz, o.pack_conv1x1(np.ascontiguousarray(w.T)), w.shape[0], w.shape[1], ("ds", 0))
+
+
+def deconv_weight_grad(x, dz, kernel, stride, pad, dtype=rdlib.RD_BF16, split=0, lib=None, alloc=None):
+    """dL/dW (Cin, Cout, 3, KW) float32 of a transposed conv with kernel (3, KW), stride (1, s), pad (1, p) from its input x (B, H, Win, Cin)
+    and dz (B, H, s Win, Cout); deterministic"""
+    return _ops(dtype, lib, alloc).deconv_weight_grad(x, dz, tuple(kernel)[1], tuple(stride)[1], tuple(pad)[1], split=split)
+
+
+def deconv_data_grad(dz, w_iohw, stride, pad, residual=None, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """dL/dx (B, H, Win, Cin) of the same transposed conv: one 3x3 launch on dz read as (B, H, Win, s Cout); w (Cin, Cout, 3, KW) float32 on
+    the host (packed on every call); residual: another gradient of x, added in the epilogue"""
+    o = _ops(dtype, lib, alloc)
+    return o.deconv_data_grad(dz, o.pack_deconv_data_grad(w_iohw, tuple(stride)[1], tuple(pad)[1]), residual)
+
+
+def batch_norm_relu_add_forward(z, a, b, r, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """y = relu(fmaf(z, a, b)) + r, the join of an aggregation stage; a, b float32 host vectors of C values"""
+    o = _ops(dtype, lib, alloc)
+    C = int(z.shape[3])
+    return o.affine_relu_add(z, _vec(o, a, C, "a"), _vec(o, b, C, "b"), r)
 
 
 def _bn_params(bn, what):
@@ -275,6 +297,123 @@ class DownBlockTrain(_BlockTrain):
         if (cin, cout) not in ((64, 64), (64, 128), (128, 128)):
             raise NotImplementedError("%s: %d -> %d channels; the strided units of the network are 64 -> 64, 64 -> 128 and 128 -> 128" % (name, cin, cout))
         self._build(name, w1, w2, cin, cout, bn1, bn2, sc_w, sc_bn, dtype, eps, momentum, lib, alloc)
+
+
+class AggStageTrain:
+    """One `agg` stage of the DLA backbone in training mode (dla_backbone.py agg_stage, _AGG_PLAN):
+
+        Deconvolution(up) -> BatchNorm (batch statistics) -> ReLU -> add(skip, .) -> res stage
+
+      name               the stage's name (agg1, agg2, agg2a, agg3): parameters are <name>_deconv_weight, <name>_deconv_bn_gamma | beta, the
+                         auxiliary states <name>_deconv_bn_moving_mean | moving_var, and those of the res stage (<name>_res_unit*)
+      deconv_w           (Cin, Cout, 3, KW) float32, MXNet's Deconvolution layout
+      deconv_bn          (gamma, beta, moving_mean, moving_var) or a dict of these, Cout values each
+      res_stage          the ResStageTrain that follows the add (Cout -> Cout, stride 1), or None: the stage ends at the add
+      kernel, stride, pad   (3, KW), (1, s), (1, p): (3, 4) / (1, 2) / (1, 1) or (3, 8) / (1, 4) / (1, 2), at the channel pairs of the shipped
+                         configs -- 128 -> 128 and 128 -> 64 for (3, 8), 128 -> 64 and 64 -> 64 for (3, 4)
+    up is (B, H, Win, Cin), skip (B, H, s Win, Cout).
+
+        forward(skip, up) -> y       z = deconv(up)                          deconv_unscaled (rd_deconv2d_bn_act_all, unscaled, no activation)
+                                     a, b = fold(stats(z))                   bn_stats, bn_fold (the moving statistics move on the device)
+                                     t = relu(a z + b) + skip                affine_relu_add (rd_affine_relu_add: the ReLU before the add)
+                                     y = res_stage.forward(t)
+        backward(g, add_to_up=None) -> (d_skip, d_up, grads)
+                                     g_t, grads = res_stage.backward(g)
+                                     d_skip = g_t                            the same tensor, no copy
+                                     dz, dgamma, dbeta = bn_relu_bwd(g_t, z) the mask [a z + b > 0] is recomputed from z
+                                     dW = deconv_weight_grad(up, dz)         rd_deconv_bwd_weight, (Cin, Cout, 3, KW) float32
+                                     d_up = deconv_data_grad(dz)             ONE persistent 3x3 launch on dz read as (B, H, Win, s Cout)
+
+    add_to_up (B, H, Win, Cin) is another gradient arriving at `up` (res2 and agg2 feed two consumers each in the graph): it is the residual
+    of the data-gradient launch, one float32 add on the accumulator and one rounding.  Every conv output and every dz is rounded once to the
+    activation type, as in BasicBlockTrain.  The data-gradient launch multiplies the structurally zero third of its weight image too.
+    Keeps skip, up, z, t, saved, y from forward() and g, g_t, dz, d_up from backward().  aux() and optimizer_entries() as in the blocks; the
+    deconv weight's entry asks for a re-pack of both images (pack=dict(deconv=(KW, s, p), ...)), so the forward() after SGD.step() runs on
+    the new weights.  Nothing synchronises with the host.
+    Refused with NotImplementedError: other kernels, strides, pads or channel pairs; a skip whose shape is not (B, H, s Win, Cout)."""
+
+    def __init__(self, name, deconv_w, deconv_bn, res_stage, kernel, stride, pad, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM,
+                 lib=None, alloc=None):
+        kernel, stride, pad = tuple(kernel), tuple(stride), tuple(pad)
+        if len(kernel) != 2 or len(stride) != 2 or len(pad) != 2 or kernel[0] != 3 or stride[0] != 1 or pad[0] != 1:
+            raise NotImplementedError("%s: kernel %r, stride %r, pad %r -- (3, KW), (1, s), (1, p)" % (name, kernel, stride, pad))
+        w = np.ascontiguousarray(deconv_w, dtype=np.float32)
+        if w.ndim != 4 or tuple(w.shape[2:]) != kernel:
+            raise NotImplementedError("%s: a (Cin, Cout, %d, %d) weight for kernel %r, got %r" % (name, kernel[0], kernel[1], kernel, w.shape))
+        self.name = name
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        self.fwd = o.pack_deconv_unscaled(w, stride[1], pad[1])          # (the form and channel checks)
+        self.bwd = o.pack_deconv_data_grad(w, stride[1], pad[1])
+        self.cin, self.cout, self.kw, self.s, self.p = self.fwd[3]
+        self.master = o.A.upload(w)
+        what = name + "_deconv_bn"
+        self.bn = {k: _vec(o, v, self.cout, "%s_%s" % (what, k)) for k, v in zip(_BN_KEYS, _bn_params(deconv_bn, what))}
+        self.eps, self.momentum = float(eps), float(momentum)
+        self.res = res_stage
+        self.up = self.saved = None
+
+    @classmethod
+    def from_params(cls, stage, arg_params, aux_params, num_block, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        """An `agg` stage of the reference from its parameter dicts: <stage>_deconv_weight, <stage>_deconv_bn_gamma | beta in arg_params,
+        <stage>_deconv_bn_moving_mean | moving_var in aux_params, and the units <stage>_res_unit1 .. <stage>_res_unit<num_block>
+        (ResStageTrain.from_params).  Kernel, stride and pad are those of the stage's name in the backbone's plan."""
+        from .symbol.backbone.dla_backbone import _AGG_PLAN
+        plan = {row[0]: row[3:] for row in _AGG_PLAN}
+        if stage not in plan:
+            raise ValueError("%s: not an agg stage of the backbone (%s)" % (stage, ", ".join(sorted(plan))))
+        kernel, stride, pad = plan[stage]
+        pre = stage + "_deconv_bn_"
+        bn = dict(gamma=arg_params[pre + "gamma"], beta=arg_params[pre + "beta"], moving_mean=aux_params[pre + "moving_mean"],
+                  moving_var=aux_params[pre + "moving_var"])
+        res = ResStageTrain.from_params(stage + "_res", arg_params, aux_params, num_block, dtype=dtype, lib=lib, alloc=alloc)
+        return cls(stage, arg_params[stage + "_deconv_weight"], bn, res, kernel, stride, pad, dtype=dtype, lib=lib, alloc=alloc)
+
+    def forward(self, skip, up, unbiased=True):
+        o, bn = self.ops, self.bn
+        B, H, Win, C = _check16(up, "up")
+        if C != self.cin:
+            raise ValueError("%s: up has %d channels, the transposed conv takes %d" % (self.name, C, self.cin))
+        if _check16(skip, "skip") != (B, H, self.s * Win, self.cout):
+            raise NotImplementedError("%s: skip %r with up %r -- the skip is (B, H, %d Win, %d) = %r" % (
+                self.name, tuple(skip.shape), tuple(up.shape), self.s, self.cout, (B, H, self.s * Win, self.cout)))
+        z = o.deconv_unscaled(up, self.fwd)
+        mean, var = o.bn_stats(z, tag="d")
+        rstd, a, b = o.bn_fold(mean, var, bn["gamma"], bn["beta"], bn["moving_mean"], bn["moving_var"], B * H * self.s * Win, self.cout,
+                               self.eps, self.momentum, unbiased, tag="d")
+        t = o.affine_relu_add(z, a, b, skip)
+        y = t if self.res is None else self.res.forward(t, unbiased)
+        self.skip, self.up, self.z, self.t, self.saved, self.y = skip, up, z, t, dict(a=a, b=b, mean=mean, var=var, rstd=rstd), y
+        return y
+
+    def backward(self, g, add_to_up=None):
+        if self.up is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(skip, up)")
+        o, nm = self.ops, self.name
+        g_t, grads = (g, {}) if self.res is None else self.res.backward(g)
+        dz, grads[nm + "_deconv_bn_gamma"], grads[nm + "_deconv_bn_beta"] = o.bn_relu_bwd(g_t, self.z, self.saved, self.bn["gamma"], tag="d")
+        grads[nm + "_deconv_weight"] = o.deconv_weight_grad(self.up, dz, self.kw, self.s, self.p)
+        d_up = o.deconv_data_grad(dz, self.bwd, residual=add_to_up)
+        self.g, self.g_t, self.dz, self.d_up = g, g_t, dz, d_up
+        return g_t, d_up, grads
+
+    def aux(self):
+        A = self.ops.A
+        out = {"%s_deconv_bn_%s" % (self.name, k): A.view_f32(self.bn[k], (self.cout,)) for k in ("moving_mean", "moving_var")}
+        if self.res is not None:
+            out.update(self.res.aux())
+        return out
+
+    def optimizer_entries(self):
+        """the deconv weight with a re-pack request for both of its images, the BatchNorm vectors, then the res stage's entries"""
+        o, nm = self.ops, self.name
+        A, shape, C = o.A, (self.cin, self.cout, 3, self.kw), self.cout
+        yield dict(name=nm + "_deconv_weight", weight=A.view_f32(self.master, shape),
+                   grad=A.view_f32(o.buf(("dWd", 0), self.cin * self.cout * 3 * self.kw * 4), shape),
+                   pack=dict(deconv=(self.kw, self.s, self.p), fwd=self.fwd[0], bwd=self.bwd[0], phase_bytes=self.fwd[2], dtype=o.dt))
+        for k, grad in (("gamma", "bn_dgamma"), ("beta", "bn_dbeta")):
+            yield dict(name="%s_deconv_bn_%s" % (nm, k), weight=A.view_f32(self.bn[k], (C,)), grad=A.view_f32(o.buf((grad, "d"), C * 4), (C,)))
+        if self.res is not None:
+            yield from self.res.optimizer_entries()
 
 
 class ResStageTrain:

@@ -38,7 +38,9 @@ forward() and backward() run on the new weights -- no host copy, no new tower.  
 TowerOps also holds the steps of a backbone BasicBlock (the residual batch norm forward and backward, the 1x1 conv, its weight gradient, the
 data gradient with a residual added in its epilogue) and those of its stride-(1,2) form (the strided 3x3 conv, its weight and data
 gradients, the 1x1 calls on the pixel-pair view): rangedet_amd.backbone_train builds BasicBlockTrain, DownBlockTrain and ResStageTrain
-from them.
+from them.  The last group is the transposed conv of an aggregation stage -- its unscaled forward, its weight gradient
+(rd_deconv_bwd_weight), its data gradient as one 3x3 launch on the s-pixel view of dz -- and the stage's join, relu(a z + b) + skip:
+rangedet_amd.backbone_train.AggStageTrain.
 """
 import numpy as np
 
@@ -353,6 +355,94 @@ class TowerOps:
         self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(dz), cout, 0, A.ptr(img), None, A.ptr(zero_shift), rdlib.ptr(residual), cin, 0, None, 0, 0, 0,
                     None, A.ptr(out), cin, 0, B, H, W, cout, cin, 1, rdlib.RD_SCALE_FOLDED | rdlib.RD_ADD, self.dt, _stream(A))
         return _view16(A, out, (B, H, W, cin), self.dt)
+
+
+    # ---- the transposed conv and the join of an aggregation stage (rangedet_amd.backbone_train.AggStageTrain) --------------------------------
+    def _deconv_form(self, w_shape, stride, pad, what):
+        """the checks of the two transposed-conv forms -> (cin, cout, kw, s, p)"""
+        if len(w_shape) != 4 or w_shape[2] != 3:
+            raise NotImplementedError("%s: a (Cin, Cout, 3, KW) transposed-conv weight, got %r" % (what, tuple(w_shape)))
+        cin, cout, _, kw = (int(v) for v in w_shape)
+        s, p = int(stride), int(pad)
+        if (kw, s, p) not in ((4, 2, 1), (8, 4, 2)):
+            raise NotImplementedError("%s: kernel (3,%d), stride (1,%d), pad (1,%d) -- the network's forms are (3,4) / 2 / 1 and (3,8) / 4 / 2"
+                                      % (what, kw, s, p))
+        if (cin, cout) not in (((128, 128), (128, 64)) if kw == 8 else ((128, 64), (64, 64))):
+            raise NotImplementedError("%s: %d -> %d channels with kernel (3,%d) -- (3,8): 128 -> 128 or 128 -> 64; (3,4): 128 -> 64 or 64 -> 64"
+                                      % (what, cin, cout, kw))
+        return cin, cout, kw, s, p
+
+    def pack_deconv_unscaled(self, w_iohw, stride, pad):
+        """the forward images of a transposed conv with the (Cin, Cout, 3, KW) weight: its `stride` phase images one after the other, no
+        scale -> (images, zero shift, bytes of a phase, (cin, cout, kw, s, p))"""
+        w = np.ascontiguousarray(w_iohw, dtype=np.float32)
+        form = cin, cout, kw, s, p = self._deconv_form(w.shape, stride, pad, "pack_deconv_unscaled")
+        ph = [self.L.pack_deconv_weight(w, s, p, q, self.dt) for q in range(s)]
+        return self.A.upload(np.concatenate(ph)), self.A.upload(np.zeros(cout, np.float32)), int(ph[0].nbytes), form
+
+    def deconv_unscaled(self, x, packed, tag=0):
+        """z = the transposed conv of x (B, H, Win, cin) -> (B, H, s Win, cout) rounded to the activation type: rd_deconv2d_bn_act_all on the
+        unscaled phase images, zero shift, no activation; packed = pack_deconv_unscaled(W, stride, pad)"""
+        A = self.A
+        img, zero_shift, phase_bytes, (cin, cout, kw, s, p) = packed
+        B, H, Win, cx = _check16(x, "x")
+        if cx != cin:
+            raise ValueError("deconv_unscaled: x %r, the transposed conv takes %d channels" % (tuple(x.shape), cin))
+        out = self.buf(("dcz", tag), B * H * s * Win * cout * 2)
+        self.L.call("rd_deconv2d_bn_act_all", rdlib.ptr(x), cin, 0, A.ptr(img), phase_bytes, A.ptr(zero_shift), None, 0, 0, A.ptr(out), cout, 0,
+                    B, H, Win, cin, cout, 3, kw, s, p, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
+        return _view16(A, out, (B, H, s * Win, cout), self.dt)
+
+    def deconv_weight_grad(self, x, dz, kernel_w, stride, pad, tag=0, split=0):
+        """x (B, H, Win, cin), dz (B, H, s Win, cout) -> dW (cin, cout, 3, KW) float32, MXNet's Deconvolution layout (rd_deconv_bwd_weight)"""
+        A, L = self.A, self.L
+        B, H, Win, cin = _check16(x, "x")
+        cout = _check16(dz, "dz")[3]
+        _, _, kw, s, p = self._deconv_form((cin, cout, 3, kernel_w), stride, pad, "deconv_weight_grad")
+        if tuple(dz.shape[:3]) != (B, H, s * Win):
+            raise ValueError("deconv_weight_grad: x %r and dz %r -- dz is (B, H, %d Win, cout)" % (tuple(x.shape), tuple(dz.shape), s))
+        nws = L.raw("rd_deconv_bwd_weight_workspace_bytes")(B, H, Win, cin, cout, kw, s, p, split)
+        ws, out = self.buf(("bww_ws", 0), nws), self.buf(("dWd", tag), cin * cout * 3 * kw * 4)
+        L.call("rd_deconv_bwd_weight", rdlib.ptr(x), cin, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, Win, cin, cout, kw, s, p, split, self.dt,
+               A.ptr(ws), nws, _stream(A))
+        return A.view_f32(out, (cin, cout, 3, kw))
+
+    def pack_deconv_data_grad(self, w_iohw, stride, pad):
+        """the image of the transposed conv's data gradient (rd_pack_deconv_data_grad_host): a 3x3 stride-1 conv from the s cout channels of
+        dz read as (B, H, Win, s cout) to cin -> (image, zero shift, (cin, cout, kw, s, p))"""
+        w = np.ascontiguousarray(w_iohw, dtype=np.float32)
+        form = self._deconv_form(w.shape, stride, pad, "pack_deconv_data_grad")
+        return self.A.upload(self.L.pack_deconv_data_grad(w, form[3], form[4], self.dt)), self.A.upload(np.zeros(form[0], np.float32)), form
+
+    def deconv_data_grad(self, dz, image, residual=None, tag=0):
+        """dz (B, H, s Win, cout) -> the gradient (B, H, Win, cin) of the transposed conv's input; image = pack_deconv_data_grad(W, stride,
+        pad).  One persistent 3x3 launch on the s-pixel view of dz.  residual (B, H, Win, cin): another gradient of the same tensor, added
+        in the launch's epilogue -- one float32 add, one rounding, as data_grad_add does"""
+        A = self.A
+        img, zero_shift, (cin, cout, kw, s, p) = image
+        B, H, Wout, cz = _check16(dz, "dz")
+        if cz != cout or Wout % s:
+            raise ValueError("deconv_data_grad: dz %r -- (B, H, %d Win, %d)" % (tuple(dz.shape), s, cout))
+        Win = Wout // s
+        if residual is not None and _check16(residual, "residual") != (B, H, Win, cin):
+            raise ValueError("deconv_data_grad: residual %r, the input gradient is %r" % (tuple(residual.shape), (B, H, Win, cin)))
+        out = self.buf(("dcx", tag), B * H * Win * cin * 2)
+        flags = rdlib.RD_SCALE_FOLDED | (rdlib.RD_ADD if residual is not None else 0)
+        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(dz), s * cout, 0, A.ptr(img), None, A.ptr(zero_shift),
+                    None if residual is None else rdlib.ptr(residual), cin, 0, None, 0, 0, 0, None, A.ptr(out), cin, 0, B, H, Win, s * cout, cin, 1,
+                    flags, self.dt, _stream(A))
+        return _view16(A, out, (B, H, Win, cin), self.dt)
+
+    def affine_relu_add(self, z, a, b, r, tag=0):
+        """y = relu(fmaf(z, a, b)) + r, the join of an aggregation stage (rd_affine_relu_add); z, r (B, H, W, C)"""
+        A = self.A
+        B, H, W, C = _check16(z, "z")
+        if _check16(r, "r") != (B, H, W, C):
+            raise ValueError("affine_relu_add: z %r and r %r differ" % (tuple(z.shape), tuple(r.shape)))
+        out = self.buf(("bn_relu_add_y", tag), B * H * W * C * 2)
+        self.L.call("rd_affine_relu_add", rdlib.ptr(z), C, 0, A.ptr(a), A.ptr(b), rdlib.ptr(r), C, 0, A.ptr(out), C, 0, B, H, W, C, self.dt,
+                    _stream(A))
+        return _view16(A, out, (B, H, W, C), self.dt)
 
 
 BN_EPS = 1e-5 + 1e-10      # mxnext/complicate.py:26-45 (normalizer_factory(type="localbn"))

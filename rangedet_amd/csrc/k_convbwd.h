@@ -43,14 +43,30 @@ inline bool bw_weight_shape_ok(int cin, int cout) { return (cin == 64 || cin == 
 inline size_t bw_weight_ws_bytes(int B, int H, int W, int cin, int cout, int split) {
   return (size_t)bw_split(B, H, W, cout, split) * 9 * cout * cin * sizeof(float);
 }
+// The weight gradient of a transposed conv (3, KW) / stride (1, s) / pad (1, p) with KW = 2 s = s + 2 p -- the two forms of the network,
+// (3,4)/2/1 and (3,8)/4/2 -- is the same kernel with the two tensors swapped: the NARROW tensor is the deconv input x (B, H, Win, Cin),
+// its channels the M axis (the kernel's COUT), the WIDE one is dz (B, H, s Win, Cout) read at pixel stride s with the column offsets
+// kw - p, its channels the N axis (the kernel's CIN):  dW[ci][co][kh][kw] = sum x[b,hi,wi,ci] dz[b,hi-1+kh,s wi-p+kw,co] comes out in
+// MXNet's (Cin, Cout, 3, KW) layout.  A workgroup owns ONE tap column kw, as in the conv: grid (S, KW, Cin / 64).
+inline bool bw_deconv_form_ok(int kw, int s, int p) { return (kw == 4 && s == 2 && p == 1) || (kw == 8 && s == 4 && p == 2); }
+inline bool bw_deconv_shape_ok(int cin, int cout, int kw) {   // the four transposed convs of the shipped configs
+  return kw == 8 ? (cin == 128 && (cout == 128 || cout == 64)) : ((cin == 128 || cin == 64) && cout == 64);
+}
+inline long bw_deconv_split(int B, int H, int Win, int cin, int kw, int split) {
+  const long n = bw_chunks(B, H, Win), cap = split > 0 ? split : BW_WG_TARGET / (kw * (cin / BW_COB));
+  return n < cap ? n : cap;
+}
+inline size_t bw_deconv_ws_bytes(int B, int H, int Win, int cin, int cout, int kw, int split) {
+  return (size_t)bw_deconv_split(B, H, Win, cin, kw, split) * 3 * kw * cin * cout * sizeof(float);
+}
 
 struct BwdWArgs {
   const unsigned short *x, *dz;
   int x_cs, x_co, dz_cs, dz_co;
   int B, H, W, nwt, nhs;
   long nchunks;
-  float* part;   // [S][9][cout][cin]
-  int Wz;        // pixels of a dz row: W (stride 1) or W / 2 (stride (1,2)); tiles, strips and chunks are counted on the dz grid
+  float* part;   // [S][9][cout][cin]  (transposed conv: [S][3 KW][Cin][Cout])
+  int Wz;        // pixels of a dz row: W (stride 1) or W / SW; tiles, strips and chunks are counted on the dz (narrow) grid
 };
 
 // eight pixels p0, p0 + step, .. p0 + 7 step of one image row, 8 channels each.  Every address is clamped into the row and the value
@@ -87,16 +103,19 @@ __device__ __forceinline__ void bw_store_t(unsigned short (*T)[BW_RS], int c0, i
 // stride.  In a dense image a pixel is one or two whole 128-byte lines, and a load instruction already reads one pixel per eight (or
 // sixteen) lanes, so every line fetched is used in full: column 0 reads the even pixels, columns -1 and +1 the odd ones, the pixels of
 // the other parity are never touched by that workgroup.  Everything behind the loads is unchanged.
-template <int DT, int CIN, int COUT, int SW = 1>
+// KW, PW: tap columns and the pad, grid.y = KW, column offset dw = kw - PW (3, 1: the conv).  The transposed convs (above) are SW 2, KW 4,
+// PW 1 and SW 4, KW 8, PW 2 with `dz` the deconv input, `x` the deconv output gradient, CIN the deconv's Cout and COUT its Cin: at stride 4 a
+// workgroup touches every fourth pixel of the wide tensor -- whole 128-byte lines still -- and the columns kw and kw + 4 read the same ones.
+template <int DT, int CIN, int COUT, int SW = 1, int KW = 3, int PW = 1>
 __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
-  static_assert(SW == 1 || SW == 2, "stride (1,1) or (1,2)");
+  static_assert(SW == 1 || SW == 2 || SW == 4, "stride (1,1), (1,2) or (1,4)");
   constexpr int WN = CIN / 32 < 4 ? CIN / 32 : 4, WM = 4 / WN, MT = 2 / WM;
   constexpr int NXU = (BW_PT / 8) * (CIN / 8), NZU = (BW_PT / 8) * (BW_COB / 8);   // load units of an x row and of a dz row
   static_assert(NXU + NZU <= 256, "one load unit per thread");
   __shared__ __attribute__((aligned(16))) unsigned short Tx[3][CIN][BW_RS];
   __shared__ __attribute__((aligned(16))) unsigned short Tz[BW_COB][BW_RS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int S = gridDim.x, s = blockIdx.x, dw = (int)blockIdx.y - 1, cob = blockIdx.z;
+  const int S = gridDim.x, s = blockIdx.x, dw = (int)blockIdx.y - PW, cob = blockIdx.z;
   const int wn = wave % WN, wm = wave / WN;
   const bool is_x = tid < NXU, is_z = tid >= NXU && tid < NXU + NZU;
   const int u = is_x ? tid : tid - NXU;            // unit: pixel group u % 8, channel group u / 8
@@ -164,18 +183,20 @@ __global__ __launch_bounds__(256) void conv3_bwd_weight_kernel(BwdWArgs a) {
 #pragma unroll
       for (int rg = 0; rg < 16; ++rg) {
         const int co = cob * BW_COB + 32 * (wm * MT + i) + (rg & 3) + 8 * (rg >> 2) + 4 * (lane >> 5);
-        a.part[(((long)s * 9 + (3 * d + dw + 1)) * COUT + co) * CIN + ci] = acc[d][i][rg];
+        a.part[(((long)s * (3 * KW) + (KW * d + dw + PW)) * COUT + co) * CIN + ci] = acc[d][i][rg];
       }
 }
 
-// dW (OIHW) = the S partial images added in index order; thread per (tap, co, ci), ci fastest: the reads are coalesced
-__global__ __launch_bounds__(256) void bwd_weight_reduce_kernel(const float* __restrict__ part, int S, int cout, int cin, float* __restrict__ dW) {
-  const int n = 9 * cout * cin, idx = blockIdx.x * 256 + threadIdx.x;
+// dW (OIHW) = the S partial images added in index order; thread per (tap, co, ci), ci fastest: the reads are coalesced.  nt: taps (9; a
+// transposed conv: 3 KW)
+__global__ __launch_bounds__(256) void bwd_weight_reduce_kernel(const float* __restrict__ part, int S, int cout, int cin, float* __restrict__ dW,
+                                                                int nt) {
+  const int n = nt * cout * cin, idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= n) return;
   float sum = part[idx];
   for (int k = 1; k < S; ++k) sum += part[(long)k * n + idx];
   const int t = idx / (cout * cin), co = idx / cin % cout, ci = idx % cin;
-  dW[((long)co * cin + ci) * 9 + t] = sum;
+  dW[((long)co * cin + ci) * nt + t] = sum;
 }
 
 // ---- weight gradient of a 1x1 conv (the projection shortcut of a backbone BasicBlock, dla_backbone.py:34-51) --------------------------------

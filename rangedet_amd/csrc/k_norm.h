@@ -432,6 +432,42 @@ __global__ __launch_bounds__(256) void affine_add_relu_kernel(NmAddArgs a) {
   }
 }
 
+// ---- the join of an aggregation stage: y = round16(max(fmaf(z, a, b), 0) + r) ------------------------------------------------------------------
+// (dla_backbone.py agg_stage: Deconvolution -> BatchNorm -> ReLU -> add(skip, .)).  The ReLU comes BEFORE the add: max(t, 0) is t where
+// t > 0 and +0 elsewhere (a -0 or a NaN pre-activation gives +0), then one float32 add of the skip r and one rounding.  NmAddArgs with
+// ar = br = NULL; `relu` is not read.  No backward launch of its own: the up-branch gradient is rd_bn_relu_bwd on z (the mask is
+// [fmaf(z, a, b) > 0], the same comparison), the skip gradient is g itself.
+template <int DT>
+__global__ __launch_bounds__(256) void affine_relu_add_kernel(NmAddArgs a) {
+  _Pragma("clang fp contract(off)")
+  const int slots = a.C / 8, PL = 256 / slots, tid = threadIdx.x, sl = tid % slots, pl = tid / slots;
+  const long per = (long)PL * NM_UNROLL * NM_EW_ITERS, lo = blockIdx.x * per, hi = lo + per < a.npix ? lo + per : a.npix;
+  const unsigned short* zb = a.z + a.z_co + 8 * sl;
+  const unsigned short* rb = a.r + a.r_co + 8 * sl;
+  unsigned short* yb = a.y + a.y_co + 8 * sl;
+  float sa[8], sb[8];
+  nm_vec8(a.a, sl, 0.f, sa);
+  nm_vec8(a.b, sl, 0.f, sb);
+  for (long q0 = lo + pl; q0 < hi; q0 += (long)NM_UNROLL * PL) {
+    Slot16 vz[NM_UNROLL], vr[NM_UNROLL];
+    nm_load(zb, a.z_cs, q0, PL, hi, vz);
+    nm_load(rb, a.r_cs, q0, PL, hi, vr);
+#pragma unroll
+    for (int u = 0; u < NM_UNROLL; ++u) {
+      const long q = q0 + (long)u * PL;
+      float fz[8], fr[8];
+      slot_unpack<DT>(vz[u], fz);
+      slot_unpack<DT>(vr[u], fr);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float t = fmaf(fz[j], sa[j], sb[j]);
+        fz[j] = (t > 0.f ? t : 0.f) + fr[j];
+      }
+      if (q < hi) *(Slot16*)(yb + q * a.y_cs) = slot_pack<DT>(fz);
+    }
+  }
+}
+
 struct NmAddBwdArgs {
   const unsigned short *g, *z, *r;
   int g_cs, g_co, z_cs, z_co, r_cs, r_co;

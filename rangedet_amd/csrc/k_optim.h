@@ -218,6 +218,19 @@ __device__ __forceinline__ void sgd_pack_slot(const float* __restrict__ w, const
   *(Slot16*)(out + 8 * slot) = o;
 }
 
+// The eight values of one slot of a PHASE image of a transposed conv (3, KW) / stride (1, s) / pad (1, p) with KW = 2 s: pack_taps_frag(6,
+// cin, cout) on the phase's six taps in ascending (dh, dw) order, i.e. tap rows kh = 2, 1, 0 and in each the columns kw_lo + s (dw = -1 or
+// 0) then kw_lo = (phase + p) % s (one more).  w is a (Cin, Cout, 3, kwm) master; a column kw >= kwm does not exist and reads as zero (the
+// strided conv's data gradient: kwm = 3 under KW = 4).  step = 6 * (32-channel chunk) + tap, q0 the first of the slot's eight input
+// channels, r its output channel.  Shared by the optimizer's strided re-pack and rd_pack_deconv_dev.
+__device__ __forceinline__ void deconv_phase_vals(const float* __restrict__ w, int cout, int kwm, int s, int p, int phase, int step, int q0,
+                                                  int r, float (&f)[8]) {
+  const int t = step % 6, kh = 2 - t / 2, kw = (phase + p) % s + ((t & 1) ? 0 : s);
+  const float* src = w + (((long)q0 * cout + r) * 3 + kh) * kwm + (kw < kwm ? kw : 0);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) f[q] = kw < kwm ? src[(long)3 * kwm * cout * q] : 0.f;
+}
+
 // one 16-byte slot of an image of a (C, C, 3, 3) weight with stride (1,2): image 2 the forward image (fold may be NULL), 3 / 4 the data
 // gradient's phase 0 / 1; `out` is the start of that image
 template <int DT>
@@ -254,12 +267,8 @@ __device__ __forceinline__ void sgd_pack_slot_s2(const float* __restrict__ w, co
 #pragma unroll
       for (int q = 0; q < 8; ++q) f[q] = sc * src[9 * q];
     } else {
-      const int t = step % 6, c = step / 6, ky = 2 - t / 2;
-      const int kx = image == 3 ? ((t & 1) ? 1 : 3) : ((t & 1) ? 0 : 2);         // kx 3: the appended zero column
-      const int q0 = 32 * c + 16 * ks + 8 * (lane >> 5);
-      const float* src = w + (((long)q0 * C + r) * 3 + ky) * 3 + (kx == 3 ? 0 : kx);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) f[q] = kx == 3 ? 0.f : src[(long)9 * C * q];
+      // phase 0: [kx 3, the appended zero column | kx 1], phase 1: [kx 2 | kx 0]
+      deconv_phase_vals(w, C, 3, 2, 1, image - 3, step, 32 * (step / 6) + 16 * ks + 8 * (lane >> 5), r, f);
     }
     o = slot_pack<DT>(f);
   }
@@ -278,6 +287,45 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const unsigned char* __re
   }
   sgd_pack_slot<DT>(e.w, e.fold, e.cout, e.cin, pk.image, (long)pk.run * SGD_PACK_SLOTS + threadIdx.x, pk.image ? e.bwd : e.fwd,
                     sgd_ntaps(e.n, e.cout, e.cin));
+}
+
+// ---- the images of a transposed conv (3, KW) / stride (1, s) / pad (1, p), KW = 2 s, from its (Cin, Cout, 3, KW) float32 master -------------
+// mode 0: the s forward phase images, pack_taps_frag(6, cin, cout) each with its zero tail (rd_pack_deconv_weight_folded_host without a
+//         scale), phase ph at ph * phase_stride elements of `out`
+// mode 1: the data-gradient image: pack_taps_frag(9, s cout, cin) of Wv[ci][e cout + co][kh][dwv + 1] = W[ci][co][kh][s dwv + e + p] (zero
+//         where that column does not exist) -- the 3x3 stride-1 conv over the gradient read as [H][Win][s Cout] -- and its zero tail
+// One thread per 16-byte slot; grid = ceil(slots / 256).
+__host__ __device__ inline long deconv_phase_slots(int cin, int cout) { return (long)(12 * cin * cout + (int)RD_CONV_TAIL) / 16; }
+__host__ __device__ inline long deconv_dgrad_slots(int cin, int cout, int s) { return (long)(18 * s * cin * cout + (int)RD_CONV_TAIL) / 16; }
+template <int DT>
+__global__ __launch_bounds__(256) void pack_deconv_dev_kernel(const float* __restrict__ w, int cin, int cout, int kw, int s, int p, int mode,
+                                                              long phase_stride, unsigned short* __restrict__ out) {
+  _Pragma("clang fp contract(off)")
+  const long g = (long)blockIdx.x * SGD_PACK_SLOTS + threadIdx.x;
+  const long per = mode ? deconv_dgrad_slots(cin, cout, s) : deconv_phase_slots(cin, cout);
+  const long body = mode ? (long)18 * s * cin * cout / 16 : (long)12 * cin * cout / 16;
+  if (g >= (mode ? per : per * s)) return;
+  const int phase = mode ? 0 : (int)(g / per);
+  const long slot = g - phase * per;
+  Slot16 o = {0u, 0u, 0u, 0u};
+  if (slot < body) {
+    const int ncb = (mode ? cin : cout) / 32, sl = (int)slot, lane = sl & 63, cb = (sl >> 6) % ncb, u = sl / (64 * ncb);
+    const int ks = u & 1, step = u >> 1;           // step = (32-channel chunk) * taps + tap
+    const int r = 32 * cb + conv_row_perm(lane & 31);
+    float f[8];
+    if (mode == 0) {
+      deconv_phase_vals(w, cout, kw, s, p, phase, step, 32 * (step / 6) + 16 * ks + 8 * (lane >> 5), r, f);
+    } else {
+      const int t = step % 9, q0 = 32 * (step / 9) + 16 * ks + 8 * (lane >> 5);      // q0: view channel e cout + co
+      const int e = q0 / cout, co = q0 - e * cout, kx = s * (t % 3 - 1) + e + p;
+      const bool in = kx >= 0 && kx < kw;
+      const float* src = w + (((long)r * cout + co) * 3 + t / 3) * kw + (in ? kx : 0);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = in ? src[(long)3 * kw * q] : 0.f;
+    }
+    o = slot_pack<DT>(f);
+  }
+  *(Slot16*)(out + phase * phase_stride + 8 * slot) = o;
 }
 
 // the single-tensor form: grid = ceil(slots / 256)

@@ -1150,7 +1150,7 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   else if (cin == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 64>), grid, dim3(256), st, a);
   else if (cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128>), grid, dim3(256), st, a);
   else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
-  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW, 9);
   return check_launch("conv3x3_bwd_weight");
 }
 // the same with a stride: stride_w 1 forwards to the entry above (its bytes, its partial count, its workspace); stride_w 2 is the weight
@@ -1193,8 +1193,48 @@ int rd_conv3x3_bwd_weight_ex(const void* x, int x_cstride, int x_coff, const voi
   else if (cin == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 64, 2>), grid, dim3(256), st, a);
   else if (cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128, 2>), grid, dim3(256), st, a);
   else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64, 2>), grid, dim3(256), st, a);
-  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW, 9);
   return check_launch("conv3x3_bwd_weight_ex");
+}
+// the weight gradient of a transposed conv (k_convbwd.h): the same kernel with the deconv input as the narrow tensor and dz as the wide one
+size_t rd_deconv_bwd_weight_workspace_bytes(int B, int H, int Win, int cin, int cout, int kw, int stride_w, int pad_w, int split) {
+  return split >= 0 && bhw_ok(B, H, Win) && bw_deconv_form_ok(kw, stride_w, pad_w) && bw_deconv_shape_ok(cin, cout, kw)
+             ? bw_deconv_ws_bytes(B, H, Win, cin, cout, kw, split) : 0;
+}
+int rd_deconv_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
+                         int Win, int cin, int cout, int kw, int stride_w, int pad_w, int split, int dtype, void* ws, size_t ws_bytes,
+                         void* stream) {
+  RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "deconv_bwd_weight: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "deconv_bwd_weight: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "deconv_bwd_weight: split %d (0: the library's choice)", split);
+  RD_REQUIRE(bw_deconv_form_ok(kw, stride_w, pad_w), RD_ESHAPE,
+             "deconv_bwd_weight: kernel (3,%d), stride (1,%d), pad (1,%d) -- (3,4) / 2 / 1 or (3,8) / 4 / 2", kw, stride_w, pad_w);
+  RD_REQUIRE(bhw_ok(B, H, Win) && (long)Win * stride_w <= 0x7fffffffL, RD_ESHAPE, "deconv_bwd_weight: B %d, H %d, Win %d", B, H, Win);
+  RD_REQUIRE(bw_deconv_shape_ok(cin, cout, kw), RD_ESHAPE,
+             "deconv_bwd_weight: %d -> %d channels with kernel (3,%d) -- (3,8): 128 -> 128 or 128 -> 64; (3,4): 128 -> 64 or 64 -> 64", cin, cout, kw);
+  RD_REQUIRE(nhwc16_ok(x_cstride, x_coff, cin) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
+             "deconv_bwd_weight: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dz) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)dW) % 4 == 0, RD_EINVAL,
+             "deconv_bwd_weight: x and dz must be 16-byte aligned, dW and the workspace 4-byte aligned");
+  const size_t need = bw_deconv_ws_bytes(B, H, Win, cin, cout, kw, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "deconv_bwd_weight: workspace %zu < %zu bytes", ws_bytes, need);
+  const long S = bw_deconv_split(B, H, Win, cin, kw, split);
+  RD_REQUIRE(S <= 0x7fffffffL, RD_ESHAPE, "deconv_bwd_weight: split %ld", S);
+  BwdWArgs a;   // the kernel's dz is the narrow tensor (the deconv input), its x the wide one (the gradient at the deconv output)
+  a.x = (const unsigned short*)dz; a.dz = (const unsigned short*)x;
+  a.x_cs = dz_cstride; a.x_co = dz_coff; a.dz_cs = x_cstride; a.dz_co = x_coff;
+  a.B = B; a.H = H; a.W = Win * stride_w; a.Wz = Win; a.nwt = (Win + BW_PT - 1) / BW_PT; a.nhs = (H + BW_RH - 1) / BW_RH;
+  a.nchunks = bw_chunks(B, H, Win);
+  a.part = (float*)ws;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, kw, cin / BW_COB);
+  if (kw == 8 && cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 128, 128, 4, 8, 2>), grid, dim3(256), st, a);
+  else if (kw == 8) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128, 4, 8, 2>), grid, dim3(256), st, a);
+  else if (cin == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128, 2, 4, 1>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64, 2, 4, 1>), grid, dim3(256), st, a);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((3 * kw * cin * cout + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cin, cout, dW,
+                     3 * kw);
+  return check_launch("deconv_bwd_weight");
 }
 
 size_t rd_conv1x1_bwd_weight_workspace_bytes(int B, int H, int W, int cin, int cout, int split) {
@@ -1381,6 +1421,28 @@ int rd_affine_add_relu(const void* z, int z_cstride, int z_coff, const float* a,
   return check_launch("affine_add_relu");
 }
 
+// the join of an aggregation stage: the ReLU before the add
+int rd_affine_relu_add(const void* z, int z_cstride, int z_coff, const float* a, const float* b, const void* r, int r_cstride, int r_coff,
+                       void* y, int y_cstride, int y_coff, int B, int H, int W, int C, int dtype, void* stream) {
+  RD_REQUIRE(z && a && b && r && y, RD_EINVAL, "affine_relu_add: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "affine_relu_add: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "affine_relu_add: B %d, H %d, W %d", B, H, W);
+  RD_REQUIRE(nm_channels_ok(C), RD_ESHAPE, "affine_relu_add: C %d (8, 16, 32, 64, 128 or 256)", C);
+  RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, C) && nhwc16_ok(r_cstride, r_coff, C) && nhwc16_ok(y_cstride, y_coff, C), RD_ESHAPE,
+             "affine_relu_add: channel strides and offsets are multiples of 8 with coff + C <= cstride");
+  RD_REQUIRE(((uintptr_t)z | (uintptr_t)r | (uintptr_t)y) % 16 == 0 && ((uintptr_t)a | (uintptr_t)b) % 4 == 0, RD_EINVAL,
+             "affine_relu_add: the tensors must be 16-byte aligned, a and b 4-byte aligned");
+  NmAddArgs f;
+  f.z = (const unsigned short*)z; f.z_cs = z_cstride; f.z_co = z_coff; f.r = (const unsigned short*)r; f.r_cs = r_cstride; f.r_co = r_coff;
+  f.a = a; f.b = b; f.ar = nullptr; f.br = nullptr; f.relu = 1;
+  f.y = (unsigned short*)y; f.y_cs = y_cstride; f.y_co = y_coff; f.C = C; f.npix = (long)B * H * W;
+  const long nb = nm_ew_blocks(f.npix, C);
+  RD_REQUIRE(nb <= 0x7fffffffL, RD_ESHAPE, "affine_relu_add: %ld pixels", f.npix);
+  hipStream_t st = (hipStream_t)stream;
+  RD_LAUNCH_H16(dtype, (affine_relu_add_kernel<DT>), dim3((unsigned)nb), dim3(256), st, f);
+  return check_launch("affine_relu_add");
+}
+
 size_t rd_bn_add_relu_bwd_workspace_bytes(int B, int H, int W, int C, int split, int projection) {
   return bhw_ok(B, H, W) && nm_channels_ok(C) && split >= 0 ? (size_t)nm_parts((long)B * H * W, split) * (projection ? 3 : 2) * C * sizeof(float) : 0;
 }
@@ -1477,6 +1539,46 @@ int rd_pack_conv3x3_dev(const float* w_dev, const float* fold_scale_dev, int cou
   RD_LAUNCH_H16(dtype, (pack_conv3x3_dev_kernel<DT>), dim3(grid), dim3(256), (hipStream_t)stream, w_dev, fold_scale_dev, cout, cin, flip ? 1 : 0,
                 (unsigned short*)out_dev);
   return check_launch("pack_conv3x3_dev");
+}
+
+// the data gradient of a transposed conv as a 3x3 stride-1 conv over dz read as [H][Win][s Cout]: its weight image, host and device
+static bool deconv_train_ok(int cin, int cout, int kw, int stride_w, int pad_w) {
+  return bw_deconv_form_ok(kw, stride_w, pad_w) && bw_deconv_shape_ok(cin, cout, kw);
+}
+int rd_pack_deconv_data_grad_host(const float* w, int cin, int cout, int kw, int stride_w, int pad_w, int dtype, void* out) {
+  RD_REQUIRE(w && out, RD_EINVAL, "pack_deconv_data_grad: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_deconv_data_grad: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(deconv_train_ok(cin, cout, kw, stride_w, pad_w), RD_ESHAPE,
+             "pack_deconv_data_grad: %d -> %d channels, kernel (3,%d), stride (1,%d), pad (1,%d) -- the four transposed convs of the network",
+             cin, cout, kw, stride_w, pad_w);
+  const int cv = stride_w * cout;
+  std::vector<float> wv((size_t)cin * cv * 9, 0.f);   // Wv[ci][e cout + co][kh][dwv + 1] = W[ci][co][kh][s dwv + e + p]
+  for (int ci = 0; ci < cin; ++ci)
+    for (int c2 = 0; c2 < cv; ++c2)
+      for (int kh = 0; kh < 3; ++kh)
+        for (int d = 0; d < 3; ++d) {
+          const int kx = stride_w * (d - 1) + c2 / cout + pad_w;
+          if (kx >= 0 && kx < kw) wv[(((size_t)ci * cv + c2) * 3 + kh) * 3 + d] = w[(((size_t)ci * cout + c2 % cout) * 3 + kh) * kw + kx];
+        }
+  return rd_pack_conv3x3_ex_host(wv.data(), nullptr, cin, cv, 1, cv, dtype, out);
+}
+int rd_pack_deconv_dev(const float* w_dev, int cin, int cout, int kw, int stride_w, int pad_w, int data_grad, long w_phase_bytes, int dtype,
+                       void* out_dev, void* stream) {
+  RD_REQUIRE(w_dev && out_dev, RD_EINVAL, "pack_deconv_dev: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_deconv_dev: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(deconv_train_ok(cin, cout, kw, stride_w, pad_w), RD_ESHAPE,
+             "pack_deconv_dev: %d -> %d channels, kernel (3,%d), stride (1,%d), pad (1,%d) -- the four transposed convs of the network", cin, cout,
+             kw, stride_w, pad_w);
+  RD_REQUIRE((uintptr_t)out_dev % 16 == 0 && (uintptr_t)w_dev % 4 == 0, RD_EINVAL,
+             "pack_deconv_dev: the image must be 16-byte aligned, the weight 4-byte aligned");
+  const long per = data_grad ? deconv_dgrad_slots(cin, cout, stride_w) : deconv_phase_slots(cin, cout);
+  RD_REQUIRE(data_grad || (w_phase_bytes >= per * 16 && w_phase_bytes % 16 == 0), RD_EINVAL,
+             "pack_deconv_dev: w_phase_bytes %ld (a multiple of 16, at least the %ld bytes of a phase image)", w_phase_bytes, per * 16);
+  const long total = data_grad ? per : per * stride_w;
+  RD_LAUNCH_H16(dtype, (pack_deconv_dev_kernel<DT>), dim3((unsigned)((total + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS)), dim3(256),
+                (hipStream_t)stream, w_dev, cin, cout, kw, stride_w, pad_w, data_grad ? 1 : 0, data_grad ? 0L : w_phase_bytes / 2,
+                (unsigned short*)out_dev);
+  return check_launch("pack_deconv_dev");
 }
 
 // ---- profiling -------------------------------------------------------------------------------------------------

@@ -145,6 +145,13 @@ SIGNATURES = {
     "rd_conv1x1_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rd_conv1x1_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_deconv_bwd_weight_workspace_bytes": (c_size_t, [c_int] * 9),
+    "rd_deconv_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_pack_deconv_data_grad_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rd_pack_deconv_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "rd_affine_relu_add": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_void_p]),
     "rd_head_out_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rd_head_out_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
@@ -310,6 +317,15 @@ class Lib:
         fs = None if fold_scale is None else np.ascontiguousarray(fold_scale, dtype=np.float32)
         self.call("rd_pack_deconv_weight_folded_host", w.ctypes.data, None if fs is None else fs.ctypes.data, cin, cout, kh, kw,
                   stride_w, pad_w, phase, dtype, out.ctypes.data)
+        return out
+
+    def pack_deconv_data_grad(self, w_iohw, stride_w, pad_w, dtype):
+        """the image of a transposed conv's data gradient: the 3x3 stride-1 conv over dz read as [H][Win][stride_w * cout]"""
+        w = np.ascontiguousarray(w_iohw, dtype=np.float32)
+        cin, cout, kh, kw = w.shape
+        assert kh == 3
+        out = np.zeros(self.cdll.rd_conv3x3_ex_packed_bytes(stride_w * cout, cin, 1, stride_w * cout), dtype=np.uint8)
+        self.call("rd_pack_deconv_data_grad_host", w.ctypes.data, cin, cout, kw, stride_w, pad_w, dtype, out.ctypes.data)
         return out
 
     def pack_deconv_phase_pair(self, img_a, img_b, cin, dtype):

@@ -8,7 +8,9 @@ takes the learning rate from a scheduler (tools/train.py:268-291, utils/lr_sched
     out = tower.forward(x); dx, grads = tower.backward(d_out); opt.step()      # the next forward() runs on the new weights
 
 A step is rd_sgd_mom_update on a table of all registered tensors (csrc/k_optim.h): one launch updates the float32 master weights and
-momenta, a second rewrites the 16-bit conv weight images the persistent conv reads from the updated masters.  Nothing goes through the
+momenta, a second rewrites the 16-bit conv weight images the persistent conv reads from the updated masters.  The images of a transposed
+conv (an `agg` stage's Deconvolution) are not in the table: step() re-packs them with one rd_pack_deconv_dev launch each, behind the
+update.  Nothing goes through the
 host and nothing synchronises; the table is built and uploaded on the first step and again only when a registered buffer has moved.
 Per element, float32, one rounding per operation (MXNet's mp_sgd_mom_update as documented; not pinned by a run of the reference):
     g = rescale_grad * grad;  g = clip(g, -clip_gradient, clip_gradient) if clip_gradient >= 0
@@ -124,7 +126,11 @@ class SGD:
         with 64 or 128 channels on either side: dict(fwd=, bwd=, fold_scale=, dtype=) -- the device buffers of the forward image (with an optional
         device vector of cout scales folded in) and of the data-gradient image, either may be None; both are rewritten by every step.  With
         stride_w=2 in the dict (a (C, C, 3, 3) weight) they are the images of the stride-(1,2) launches (rd_sgd_tensor_t.stride_w).  wd_mult
-        None: 1 for names ending in _weight or _gamma, else 0.  Registering a name again replaces its buffers and keeps its momentum."""
+        None: 1 for names ending in _weight or _gamma, else 0.  Registering a name again replaces its buffers and keeps its momentum.
+        pack = dict(deconv=(KW, stride, pad), fwd=, bwd=, dtype=[, phase_bytes=]) on a (Cin, Cout, 3, KW) transposed-conv weight: the table
+        updates the master as a plain tensor without images, and step() then issues one rd_pack_deconv_dev launch per named image on the
+        same stream -- fwd, the `stride` phase images rd_deconv2d_bn_act_all reads (phase_bytes apart; default: packed back to back), and
+        bwd, the image of the data gradient.  Nothing synchronises."""
         _check_f32(weight, name)
         _check_f32(grad, name + " gradient")
         n = _numel(weight)
@@ -132,7 +138,22 @@ class SGD:
             raise ValueError("%s: %d weight and %d gradient elements (equal, at least one)" % (name, n, _numel(grad)))
         e = dict(weight=weight, grad=grad, n=n, shape=tuple(int(v) for v in weight.shape), lr_mult=float(lr_mult),
                  wd_mult=default_wd_mult(name) if wd_mult is None else float(wd_mult), cout=0, cin=0, fwd=None, bwd=None, fold=None, stride_w=0)
-        if pack is not None:
+        if pack is not None and pack.get("deconv") is not None:
+            # a transposed-conv master (Cin, Cout, 3, KW): a plain n-element tensor of the table; step() re-packs its images afterwards
+            shp = e["shape"]
+            kw, s, p = (int(v) for v in pack["deconv"])
+            if len(shp) != 4 or shp[2:] != (3, kw) or (kw, s, p) not in ((4, 2, 1), (8, 4, 2)):
+                raise NotImplementedError("%s: deconv=%r images of a %r weight -- a (Cin, Cout, 3, KW) transposed-conv weight of the forms "
+                                          "(KW, stride, pad) = (4, 2, 1) or (8, 4, 2)" % (name, tuple(pack["deconv"]), shp))
+            dt = pack.get("dtype", rdlib.RD_BF16)
+            if dt not in rdlib.H16 or self._dtype not in (None, dt):
+                raise ValueError("%s: image type %r; one 16-bit type (RD_BF16 / RD_F16) per optimizer" % (name, dt))
+            phase_bytes = int(pack.get("phase_bytes") or self.L.cdll.rd_conv_packed_bytes(6, shp[0], shp[1], dt))
+            e["deconv"] = dict(form=(shp[0], shp[1], kw, s, p), fwd=pack.get("fwd"), bwd=pack.get("bwd"), phase_bytes=phase_bytes, dtype=dt)
+            for k in ("fwd", "bwd"):
+                if e["deconv"][k] is not None and rdlib.ptr(e["deconv"][k]) % 16:
+                    raise ValueError("%s: %s buffer at %#x is not 16-byte aligned" % (name, k, rdlib.ptr(e["deconv"][k])))
+        elif pack is not None:
             shp = e["shape"]
             if len(shp) != 4 or shp[2:] not in ((3, 3), (1, 1)) or shp[0] not in (64, 128) or shp[1] not in (64, 128):
                 raise NotImplementedError("%s: weight images of shape %r -- a (cout, cin, 3, 3) or (cout, cin, 1, 1) conv weight with 64 or 128 "
@@ -186,6 +207,15 @@ class SGD:
         self.num_update += 1
         lr = self.lr if self.lr_scheduler is None else float(self.lr_scheduler(self.num_update))
         A = self.A
+        stream = A.stream_ptr(None) if hasattr(A, "stream_ptr") else A.stream
         self.L.call("rd_sgd_mom_update", A.ptr(self._dev), self._host.ctypes.data, lr, self.momentum, self.wd, self.rescale_grad,
-                    self.clip_gradient, A.stream_ptr(None) if hasattr(A, "stream_ptr") else A.stream)
+                    self.clip_gradient, stream)
+        for e in self._entries.values():          # the transposed-conv images: one launch each, behind the update on the same stream
+            d = e.get("deconv")
+            if d is None:
+                continue
+            for key, data_grad in (("fwd", 0), ("bwd", 1)):
+                if d[key] is not None:
+                    self.L.call("rd_pack_deconv_dev", rdlib.ptr(e["weight"]), *d["form"], data_grad, d["phase_bytes"], d["dtype"],
+                                rdlib.ptr(d[key]), stream)
         return lr
