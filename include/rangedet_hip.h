@@ -527,8 +527,9 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * Training-mode normalisation (batch statistics, the gradients of gamma and beta) is the next section.  The stride-(1,2) 3x3 conv of a
  * down-sampling BasicBlock: weight gradient rd_conv3x3_bwd_weight_ex, data gradient rd_deconv2d_bn_act_all on the weight read as a (3,4)
  * transposed-conv weight with a zero fourth column; its strided 1x1 shortcut runs the 1x1 calls on the pixel-pair view (channel stride
- * 2 cin).  The network's own transposed convs: rd_deconv_bwd_weight and the packers declared with it.  Not here: the concat conv, the
- * Meta-Kernel.
+ * 2 cin).  The network's own transposed convs: rd_deconv_bwd_weight and the packers declared with it.  The Meta-Kernel unit
+ * with the folded normalisation: rd_meta_kernel_bwd_data and rd_meta_kernel_bwd_params, at the end of this section.  Not here: the concat
+ * conv, and the batch-statistics form of the Meta-Kernel's 576-channel BatchNorm.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -600,6 +601,30 @@ size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout);
 int rd_head_out_bwd(const float* d_out, long out_batch_stride, long n_off, const void* x, int x_cstride, int x_coff, const float* w,
                     int relu_mask, const float* scale, void* dx, int dx_cstride, int dx_coff, float* dw, float* dbias, int B, int H,
                     int W, int cin, int nout, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* Backward of the Meta-Kernel unit (rd_meta_kernel_fwd) up to z, with the folded normalisation s1, t1 of its 576-channel BatchNorm:
+ * dz = dL/dz comes from rd_relu_affine_bwd(g, y, s2).  RD_BF16 / RD_F16 only (RD_F32: RD_EINVAL).  The packed block of the backward is
+ * made on the host from the same nine arrays as rd_pack_meta_host (s2, t2 are not read); the kernels evaluate w_k and r_k under the
+ * forward's arithmetic contract (the packer's rounded s1 W1 and A, h rounded to the type, the centre tap's folded constant), so the
+ * gradient is that of the function rd_meta_kernel_fwd computes.  csrc/k_metabwd.h lists every 16-bit rounding.
+ *   rd_meta_kernel_bwd_data    ddata (B, H, W, 64 at g_coff) in the activation type, rounded once; residual (may be NULL): a tensor of
+ *                              the same shape added in float32 before that rounding (the identity shortcut's gradient).  No workspace.
+ *   rd_meta_kernel_bwd_params  float32: dA (64, 576) [aggregation_conv1], dW1 (64, 32), db1 (64) [mlp1], dW0 (32, 3), db0 (32) [mlp0],
+ *                              dt1 (576) = dL/dt1 and dq1 (576) = sum dr (r - t1) (index c 9 + k; dq1 / gamma is the BatchNorm's dgamma
+ *                              under frozen statistics, and both are the sums the batch-statistics form needs).
+ * split: the most partial sums per output element, as in rd_conv3x3_bwd_weight (0: the library's choice, 64); the workspace holds
+ * split x 9 x 6464 floats at most and only partial sums.  No atomics, two calls give the same bytes, and the bytes do not depend on the
+ * CU count.  RD_EINVAL: a null pointer, a misaligned tensor, split < 0; RD_ESHAPE: B, H or W < 1, a channel stride or offset that is no
+ * multiple of 8 or coff + 64 > cstride; RD_EWORKSPACE: ws_bytes below rd_meta_kernel_bwd_workspace_bytes(B, H, W, split). */
+size_t rd_meta_bwd_packed_bytes(int dtype);
+int rd_pack_meta_bwd_host(const float* w0, const float* b0, const float* w1, const float* b1, const float* s1, const float* t1,
+                          const float* agg, const float* s2, const float* t2, int dtype, void* packed_host);
+int rd_meta_kernel_bwd_data(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                            const void* packed_bwd, const void* residual, int r_cstride, int r_coff, void* ddata, int g_cstride, int g_coff,
+                            int B, int H, int W, int dtype, void* stream);
+size_t rd_meta_kernel_bwd_workspace_bytes(int B, int H, int W, int split);
+int rd_meta_kernel_bwd_params(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                              const void* packed_bwd, float* dA, float* dW1, float* db1, float* dW0, float* db0, float* dt1, float* dq1, int B,
+                              int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- training-mode batch norm of a head-tower layer, forward and backward ----------------------------------------------------------------
  * The reference builds every tower layer with normalizer_factory(type="localbn") (mxnext/complicate.py:26-45): mx.sym.BatchNorm with

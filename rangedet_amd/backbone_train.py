@@ -248,7 +248,7 @@ class BasicBlockTrain(_BlockTrain):
     def __init__(self, name, conv1_w, conv2_w, bn1, bn2, sc_w=None, sc_bn=None, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM,
                  stride=(1, 1), meta_kernel=False, lib=None, alloc=None):
         if meta_kernel or conv1_w is None:
-            raise NotImplementedError("%s: a Meta-Kernel unit -- its first conv is the Meta-Kernel, which has no backward here" % name)
+            raise NotImplementedError("%s: a Meta-Kernel unit -- its first conv is the Meta-Kernel: rangedet_amd.backward.MetaUnitBackward carries its backward (folded normalisation)" % name)
         if tuple(stride) != (1, 1):
             raise NotImplementedError("%s: stride %r -- this class runs stride-1 units; the strided conv2 and the strided shortcut of a "
                                       "stride-(1, 2) unit (unit 1 of res2a .. res3) are DownBlockTrain" % (name, tuple(stride)))
@@ -289,7 +289,7 @@ class DownBlockTrain(_BlockTrain):
 
     def __init__(self, name, conv1_w, conv2_w, bn1, bn2, sc_w, sc_bn, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM, lib=None, alloc=None):
         if conv1_w is None:
-            raise NotImplementedError("%s: a Meta-Kernel unit -- its first conv is the Meta-Kernel, which has no backward here" % name)
+            raise NotImplementedError("%s: a Meta-Kernel unit -- its first conv is the Meta-Kernel: rangedet_amd.backward.MetaUnitBackward carries its backward (folded normalisation)" % name)
         if sc_w is None or sc_bn is None:
             raise NotImplementedError("%s: a stride-(1,2) unit without a projection -- the identity cannot halve the width; the reference gives "
                                       "every strided unit the 1x1 shortcut (sc_w, sc_bn)" % name)

@@ -41,6 +41,9 @@ gradients, the 1x1 calls on the pixel-pair view): rangedet_amd.backbone_train bu
 from them.  The last group is the transposed conv of an aggregation stage -- its unscaled forward, its weight gradient
 (rd_deconv_bwd_weight), its data gradient as one 3x3 launch on the s-pixel view of dz -- and the stage's join, relu(a z + b) + skip:
 rangedet_amd.backbone_train.AggStageTrain.
+
+The Meta-Kernel unit (res1_unit2) has its own fused backward (csrc/k_metabwd.h): meta_kernel_data_grad and meta_kernel_param_grads are
+the single steps, MetaUnitBackward the unit with inference-mode normalisation, forward through rd_meta_kernel_fwd.
 """
 import numpy as np
 
@@ -444,6 +447,49 @@ class TowerOps:
                     _stream(A))
         return _view16(A, out, (B, H, W, C), self.dt)
 
+    # ---- the Meta-Kernel unit (csrc/k_metabwd.h; MetaUnitBackward below) -----------------------------------------------------------------------
+    def _meta_check(self, dz, data, coord, what):
+        B, H, W, C = _check16(data, "data")
+        if C != 64 or _check16(dz, "dz") != (B, H, W, 64):
+            raise ValueError("%s: data %r and dz %r -- both (B, H, W, 64)" % (what, tuple(data.shape), tuple(dz.shape)))
+        if tuple(coord.shape) != (B, 3, H, W) or (coord.itemsize if isinstance(coord, np.ndarray) else coord.element_size()) != 4:
+            raise ValueError("%s: coord %r -- a float32 (B, 3, H, W) tensor" % (what, tuple(coord.shape)))
+        return B, H, W
+
+    def meta_data_grad(self, dz, data, coord, packed_bwd, residual=None, tag=0):
+        """dz, data (B, H, W, 64), coord (B, 3, H, W) float32, packed_bwd the uploaded block of Lib.pack_meta_bwd -> ddata (B, H, W, 64);
+        residual (B, H, W, 64): added in float32 before the one rounding"""
+        A = self.A
+        B, H, W = self._meta_check(dz, data, coord, "meta_data_grad")
+        if residual is not None and _check16(residual, "residual") != (B, H, W, 64):
+            raise ValueError("meta_data_grad: residual %r, the input gradient is %r" % (tuple(residual.shape), (B, H, W, 64)))
+        out = self.buf(("meta_ddata", tag), B * H * W * 128)
+        self.L.call("rd_meta_kernel_bwd_data", rdlib.ptr(dz), 64, 0, rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd),
+                    None if residual is None else rdlib.ptr(residual), 64, 0, A.ptr(out), 64, 0, B, H, W, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, 64), self.dt)
+
+    def meta_param_grads(self, dz, data, coord, packed_bwd, split=0, tag=0):
+        """-> float32 device views dA (64, 576), dW1 (64, 32), db1 (64,), dW0 (32, 3), db0 (32,), dt1 (576,), dq1 (576,), by name"""
+        A, L = self.A, self.L
+        B, H, W = self._meta_check(dz, data, coord, "meta_param_grads")
+        nws = L.raw("rd_meta_kernel_bwd_workspace_bytes")(B, H, W, split)
+        ws = self.buf(("meta_ws", 0), nws)
+        shapes = (("dA", (64, 576)), ("dW1", (64, 32)), ("db1", (64,)), ("dW0", (32, 3)), ("db0", (32,)), ("dt1", (576,)), ("dq1", (576,)))
+        bufs = [self.buf(("meta_" + k, tag), int(np.prod(shp)) * 4) for k, shp in shapes]
+        L.call("rd_meta_kernel_bwd_params", rdlib.ptr(dz), 64, 0, rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd),
+               *[A.ptr(b) for b in bufs], B, H, W, split, self.dt, A.ptr(ws), nws, _stream(A))
+        return {k: A.view_f32(b, shp) for (k, shp), b in zip(shapes, bufs)}
+
+    def meta_forward(self, data, coord, packed_fwd, tag=0):
+        """y = rd_meta_kernel_fwd(data, coord) (B, H, W, 64); packed_fwd the uploaded block of Lib.pack_meta"""
+        A = self.A
+        B, H, W, C = _check16(data, "data")
+        if C != 64 or tuple(coord.shape) != (B, 3, H, W):
+            raise ValueError("meta_forward: data %r, coord %r -- (B, H, W, 64) and (B, 3, H, W)" % (tuple(data.shape), tuple(coord.shape)))
+        out = self.buf(("meta_y", tag), B * H * W * 128)
+        self.L.call("rd_meta_kernel_fwd", rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_fwd), A.ptr(out), 64, 0, B, H, W, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, 64), self.dt)
+
 
 BN_EPS = 1e-5 + 1e-10      # mxnext/complicate.py:26-45 (normalizer_factory(type="localbn"))
 BN_MOMENTUM = 0.9
@@ -516,6 +562,84 @@ def batch_norm_relu_backward(g, z, saved, gamma, split=0, dtype=rdlib.RD_BF16, l
     """g = dL/dy, z and saved as batch_norm_relu_forward had them, gamma a float32 host vector -> (dz, dgamma, dbeta)"""
     o = _ops(dtype, lib, alloc)
     return o.bn_relu_bwd(g, z, saved, _vec(o, gamma, int(z.shape[3]), "gamma"), saved.get("relu", True), split)
+
+
+_META_KEYS = ("w0", "b0", "w1", "b1", "s1", "t1", "agg", "s2", "t2")
+
+
+def _meta_packed_bwd(o, prm):
+    """prm: the nine arrays of Lib.pack_meta by name (w0 (32, 3), b0, w1 (64, 32), b1, s1, t1 (576), agg (64, 576), s2, t2)"""
+    return o.A.upload(o.L.pack_meta_bwd(*[prm[k] for k in _META_KEYS], o.dt))
+
+
+def meta_kernel_data_grad(dz, data, coord, prm, residual=None, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """dL/ddata of the Meta-Kernel unit up to z (rd_meta_kernel_bwd_data): dz, data (B, H, W, 64) device tensors of the activation type, coord
+    (B, 3, H, W) float32 on the device, prm the folded parameters on the host (packed on every call: keep a MetaUnitBackward for repeated
+    use); residual is added in float32 before the one rounding"""
+    o = _ops(dtype, lib, alloc)
+    return o.meta_data_grad(dz, data, coord, _meta_packed_bwd(o, prm), residual)
+
+
+def meta_kernel_param_grads(dz, data, coord, prm, split=0, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+    """{dA, dW1, db1, dW0, db0, dt1, dq1}: the float32 parameter gradients of the Meta-Kernel unit up to z (rd_meta_kernel_bwd_params);
+    deterministic"""
+    o = _ops(dtype, lib, alloc)
+    return o.meta_param_grads(dz, data, coord, _meta_packed_bwd(o, prm), split)
+
+
+class MetaUnitBackward:
+    """The Meta-Kernel unit (res1_unit2: meta_kernel.py:166-240 + dla_backbone.py:92-97) with inference-mode normalisation, forward and
+    backward, built from the reference's parameter dict:
+      <name>_<W>_mlp0_weight | bias, <name>_<W>_mlp1_weight | bias      the 3 -> 32 -> 64 MLP (1x1 convs)
+      <name>point_wise_mlp_bn1_*                                        the 576-channel BatchNorm, folded to s1, t1 with its moving statistics
+      <name>aggregation_conv1_weight, <name>aggregation_bn1_*           the 576 -> 64 conv and its BatchNorm, folded to s2, t2
+    forward(data, coord) -> y (B, H, W, 64) through rd_meta_kernel_fwd (data a (B, H, W, 64) device tensor of the activation type, coord
+    (B, 3, H, W) float32).  backward(g, residual=None) -> (ddata, grads): dz = rd_relu_affine_bwd(g, y, s2), then the two fused launches of
+    csrc/k_metabwd.h; residual (the identity shortcut's gradient) is added to ddata in float32 before its one rounding.  grads: float32
+    device tensors under the reference's names and shapes for the two MLP convs and the aggregation conv, and -- under the frozen
+    statistics -- point_wise_mlp_bn1_beta = dt1, point_wise_mlp_bn1_gamma = dq1 / gamma.  The gradients of aggregation_bn1's gamma and beta
+    need z, which the fused forward never writes: they come with the training-mode form."""
+
+    def __init__(self, name, params, W, dtype=rdlib.RD_BF16, lib=None, alloc=None, eps=BN_EPS):
+        from .runtime import bn_affine
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        self.name, self.W = name, int(W)
+        pre = "%s_%d" % (name, self.W)
+        f = lambda k, shape: np.ascontiguousarray(params[k], dtype=np.float32).reshape(shape)
+        s1, t1 = bn_affine(params, name + "point_wise_mlp_bn1", eps)
+        s2, t2 = bn_affine(params, name + "aggregation_bn1", eps)
+        self.prm = dict(w0=f(pre + "_mlp0_weight", (32, 3)), b0=f(pre + "_mlp0_bias", (32,)), w1=f(pre + "_mlp1_weight", (64, 32)),
+                        b1=f(pre + "_mlp1_bias", (64,)), s1=s1, t1=t1, agg=f(name + "aggregation_conv1_weight", (64, 576)), s2=s2, t2=t2)
+        gamma = f(name + "point_wise_mlp_bn1_gamma", (576,))
+        if (gamma == 0).any():
+            raise ValueError("%spoint_wise_mlp_bn1_gamma has a zero: its gradient dq1 / gamma does not exist" % name)
+        self.names = dict(dW0=(pre + "_mlp0_weight", (32, 3, 1, 1)), db0=(pre + "_mlp0_bias", (32,)), dW1=(pre + "_mlp1_weight", (64, 32, 1, 1)),
+                          db1=(pre + "_mlp1_bias", (64,)), dA=(name + "aggregation_conv1_weight", (64, 576, 1, 1)),
+                          dt1=(name + "point_wise_mlp_bn1_beta", (576,)), dq1=(name + "point_wise_mlp_bn1_gamma", (576,)))
+        self.packed_fwd = o.A.upload(o.L.pack_meta(*[self.prm[k] for k in _META_KEYS], dtype))
+        self.packed_bwd = _meta_packed_bwd(o, self.prm)
+        self.s2 = o.A.upload(np.ascontiguousarray(s2, dtype=np.float32))
+        self.gamma = o.A.view_f32(o.A.upload(gamma), (576,))
+        self.saved = None
+
+    def forward(self, data, coord):
+        self.saved = (data, coord, self.ops.meta_forward(data, coord, self.packed_fwd))
+        return self.saved[2]
+
+    def backward(self, g, residual=None, split=0):
+        if self.saved is None:
+            raise RuntimeError("backward before forward: the input and the output are kept by forward(data, coord)")
+        o = self.ops
+        data, coord, y = self.saved
+        self.dz = dz = o.relu_affine_bwd(g, y, self.s2, tag="meta")
+        raw = o.meta_param_grads(dz, data, coord, self.packed_bwd, split)
+        grads = {}
+        for k, (pname, shape) in self.names.items():
+            v = raw[k]
+            if k == "dq1":
+                v = v / self.gamma                 # d r / d gamma = (r - t1) / gamma under the frozen statistics
+            grads[pname] = v.reshape(shape)
+        return o.meta_data_grad(dz, data, coord, self.packed_bwd, residual), grads
 
 
 class _HeadTower:

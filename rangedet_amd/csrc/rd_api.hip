@@ -12,6 +12,7 @@
 #include "k_riou.h"
 #include "k_loss.h"
 #include "k_convbwd.h"
+#include "k_metabwd.h"
 #include "k_norm.h"
 #include "k_optim.h"
 #include "k_sort.h"
@@ -1152,6 +1153,62 @@ int rd_conv3x3_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
   hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((9 * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin, dW, 9);
   return check_launch("conv3x3_bwd_weight");
+}
+// ---- backward of the Meta-Kernel unit (k_metabwd.h) ---------------------------------------------------------------------------------
+size_t rd_meta_bwd_packed_bytes(int dtype) { return is_h16(dtype) ? meta_bwd_layout().total : 0; }
+int rd_pack_meta_bwd_host(const float* w0, const float* b0, const float* w1, const float* b1, const float* s1, const float* t1,
+                          const float* agg, const float* s2, const float* t2, int dtype, void* packed_host) {
+  RD_REQUIRE(w0 && b0 && w1 && b1 && s1 && t1 && agg && s2 && t2 && packed_host, RD_EINVAL, "pack_meta_bwd: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_meta_bwd: dtype %d (RD_BF16 or RD_F16)", dtype);
+  pack_meta_bwd(w0, b0, w1, b1, s1, t1, agg, dtype, packed_host);   // (s2, t2 act behind z: rd_relu_affine_bwd)
+  return RD_OK;
+}
+static int meta_bwd_checks(const char* what, const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff,
+                           const float* coord, const void* packed, int B, int H, int W, int dtype, MetaBwdArgs& a) {
+  RD_REQUIRE(dz && data && coord && packed, RD_EINVAL, "%s: null pointer", what);
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "%s: dtype %d (RD_BF16 or RD_F16)", what, dtype);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "%s: B %d, H %d, W %d", what, B, H, W);
+  RD_REQUIRE(nhwc16_ok(dz_cstride, dz_coff, 64) && nhwc16_ok(d_cstride, d_coff, 64), RD_ESHAPE,
+             "%s: channel strides and offsets are multiples of 8 with coff + 64 <= cstride", what);
+  RD_REQUIRE(((uintptr_t)dz | (uintptr_t)data | (uintptr_t)packed) % 16 == 0 && (uintptr_t)coord % 4 == 0, RD_EINVAL,
+             "%s: dz, data and the packed block must be 16-byte aligned, coord 4-byte aligned", what);
+  a.dz = (const unsigned short*)dz; a.z_cs = dz_cstride; a.z_co = dz_coff;
+  a.data = (const unsigned short*)data; a.d_cs = d_cstride; a.d_co = d_coff;
+  a.coord = coord; a.packed = (const unsigned char*)packed;
+  a.res = nullptr; a.r_cs = a.r_co = 0; a.ddata = nullptr; a.g_cs = a.g_co = 0; a.part = nullptr;
+  a.B = B; a.H = H; a.W = W;
+  return RD_OK;
+}
+int rd_meta_kernel_bwd_data(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                            const void* packed_bwd, const void* residual, int r_cstride, int r_coff, void* ddata, int g_cstride, int g_coff,
+                            int B, int H, int W, int dtype, void* stream) {
+  MetaBwdArgs a;
+  const int rc = meta_bwd_checks("meta_kernel_bwd_data", dz, dz_cstride, dz_coff, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W, dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(ddata, RD_EINVAL, "meta_kernel_bwd_data: null pointer");
+  RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, 64) && (!residual || nhwc16_ok(r_cstride, r_coff, 64)), RD_ESHAPE,
+             "meta_kernel_bwd_data: channel strides and offsets are multiples of 8 with coff + 64 <= cstride");
+  RD_REQUIRE(((uintptr_t)ddata | (uintptr_t)residual) % 16 == 0, RD_EINVAL, "meta_kernel_bwd_data: ddata and residual must be 16-byte aligned");
+  a.res = (const unsigned short*)residual; a.r_cs = r_cstride; a.r_co = r_coff;
+  a.ddata = (unsigned short*)ddata; a.g_cs = g_cstride; a.g_co = g_coff;
+  return launch_meta_bwd_data(a, dtype, (hipStream_t)stream);
+}
+size_t rd_meta_kernel_bwd_workspace_bytes(int B, int H, int W, int split) { return bhw_ok(B, H, W) && split >= 0 ? mb_ws_bytes(B, H, W, split) : 0; }
+int rd_meta_kernel_bwd_params(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                              const void* packed_bwd, float* dA, float* dW1, float* db1, float* dW0, float* db0, float* dt1, float* dq1, int B,
+                              int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  MetaBwdArgs a;
+  const int rc = meta_bwd_checks("meta_kernel_bwd_params", dz, dz_cstride, dz_coff, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W, dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(dA && dW1 && db1 && dW0 && db0 && dt1 && dq1 && ws, RD_EINVAL, "meta_kernel_bwd_params: null pointer");
+  RD_REQUIRE(split >= 0, RD_EINVAL, "meta_kernel_bwd_params: split %d (0: the library's choice)", split);
+  RD_REQUIRE(((uintptr_t)dA | (uintptr_t)dW1 | (uintptr_t)db1 | (uintptr_t)dW0 | (uintptr_t)db0 | (uintptr_t)dt1 | (uintptr_t)dq1 | (uintptr_t)ws) % 4 == 0,
+             RD_EINVAL, "meta_kernel_bwd_params: the gradients and the workspace must be 4-byte aligned");
+  const size_t need = mb_ws_bytes(B, H, W, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "meta_kernel_bwd_params: workspace %zu < %zu bytes", ws_bytes, need);
+  a.part = (float*)ws;
+  const MetaBwdOut out{dA, dW1, db1, dW0, db0, dt1, dq1};
+  return launch_meta_bwd_params(a, out, split, dtype, (hipStream_t)stream);
 }
 // the same with a stride: stride_w 1 forwards to the entry above (its bytes, its partial count, its workspace); stride_w 2 is the weight
 // gradient of a 3x3 stride-(1,2) pad-1 conv, x (B, H, Win) against dz (B, H, Win / 2): chunks and the split are counted on the dz grid

@@ -94,6 +94,13 @@ SIGNATURES = {
     "rd_pack_meta_host": (c_int, [c_void_p] * 9 + [c_int, c_void_p]),
     "rd_meta_kernel_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_void_p]),
+    "rd_meta_bwd_packed_bytes": (c_size_t, [c_int]),
+    "rd_pack_meta_bwd_host": (c_int, [c_void_p] * 9 + [c_int, c_void_p]),
+    "rd_meta_kernel_bwd_data": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                        c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rd_meta_kernel_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rd_meta_kernel_bwd_params": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_void_p] * 7
+                                  + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "rd_sorted_foreground_workspace_bytes": (c_size_t, [c_long, c_long]),
     "rd_sorted_foreground": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -348,6 +355,14 @@ class Lib:
         assert arrs[0].shape == (32, 3) and arrs[2].shape == (64, 32) and arrs[6].shape == (64, 576)
         out = np.zeros(self.cdll.rd_meta_packed_bytes(dtype), dtype=np.uint8)
         self.call("rd_pack_meta_host", *[a.ctypes.data for a in arrs], dtype, out.ctypes.data)
+        return out
+
+    def pack_meta_bwd(self, w0, b0, w1, b1, s1, t1, agg, s2, t2, dtype):
+        """the packed block rd_meta_kernel_bwd_data / rd_meta_kernel_bwd_params read: the arrays of pack_meta, 16-bit types only"""
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (w0, b0, w1, b1, s1, t1, agg, s2, t2)]
+        assert arrs[0].shape == (32, 3) and arrs[2].shape == (64, 32) and arrs[6].shape == (64, 576)
+        out = np.zeros(max(self.cdll.rd_meta_bwd_packed_bytes(dtype), 16), dtype=np.uint8)
+        self.call("rd_pack_meta_bwd_host", *[a.ctypes.data for a in arrs], dtype, out.ctypes.data)
         return out
 
     def sgd_table(self, tensors, dtype=RD_BF16):
