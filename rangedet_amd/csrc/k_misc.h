@@ -117,8 +117,10 @@ __global__ __launch_bounds__(256) void head_out_kernel(const void* __restrict__ 
 // (HBM-bound: cin*2 bytes in, NOUT*4 bytes out per pixel).  One wave owns 32 pixels at a time.  Global loads are whole
 // pixel rows (a wave instruction = 4 pixels x 256 B contiguous), transposed through a wave-private, XOR-swizzled 8 KB
 // LDS image into the MFMA B-operand layout (lane (px, hi) <- 16-byte channel group 2*ks + hi of its pixel).  The A
-// operand is the weight matrix padded to 32 rows, held in registers as a bf16 hi + lo pair per k-step (w = hi + lo to
-// ~2^-17, so fp32 weights keep their precision); D[co][px] leaves lane (px, hi) with co = 4*hi + r in registers r = 0..3.
+// operand is the weight matrix padded to 32 rows, held in registers as 16-bit terms per k-step, so that fp32 weights keep their
+// precision: fp16 as hi + lo (11 + 11 bits, w to 2^-24 or lo's subnormal spacing); bf16 as hi + lo + lo2 -- two round-to-nearest
+// bf16 terms reach only 2^-17 |w| (8 bits each), the third makes the sum the fp32 weight itself.  The kernel is HBM-bound; the
+// third MFMA per k-step rides under the loads.  D[co][px] leaves lane (px, hi) with co = 4*hi + r in registers r = 0..3.
 template <int NOUT, int DT = RD_BF16>
 __global__ __launch_bounds__(256) void head_out_mfma_kernel(const bf16_t* __restrict__ x, int cs, int coff,
                                                             const float* __restrict__ w, const float* __restrict__ bias,
@@ -130,18 +132,22 @@ __global__ __launch_bounds__(256) void head_out_mfma_kernel(const bf16_t* __rest
   const int nks = cin >> 4, nsl = cin >> 3;                     // k-steps (<= 8), 16-byte slots per pixel (<= 16)
   x += (size_t)blockIdx.y * HW * cs + coff;
   out += (size_t)blockIdx.y * out_bs + n_off * NOUT;
-  s16x8 wh[8], wl[8];
+  constexpr bool W3 = DT == RD_BF16;                            // a third weight term (bf16 only)
+  s16x8 wh[8], wl[8], wl2[W3 ? 8 : 1];
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks) {
-    unsigned short h[8], l[8];
+    unsigned short h[8], l[8], l2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = (m < NOUT && ks < nks) ? w[m * cin + ks * 16 + hi * 8 + j] : 0.f;
       h[j] = H16<DT>::from_f32(v);
-      l[j] = H16<DT>::from_f32(v - H16<DT>::to_f32(h[j]));
+      const float r1 = v - H16<DT>::to_f32(h[j]);               // (exact: hi is v's leading bits)
+      l[j] = H16<DT>::from_f32(r1);
+      l2[j] = H16<DT>::from_f32(r1 - H16<DT>::to_f32(l[j]));
     }
     memcpy(&wh[ks], h, 16);
     memcpy(&wl[ks], l, 16);
+    if constexpr (W3) memcpy(&wl2[ks], l2, 16);
   }
   float bs[4];
 #pragma unroll
@@ -173,6 +179,7 @@ __global__ __launch_bounds__(256) void head_out_mfma_kernel(const bf16_t* __rest
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       const s16x8 b = *(const s16x8*)(img + m * 256 + (((2 * ks + hi) ^ (m & 15)) << 4));
+      if constexpr (W3) acc = H16<DT>::mfma(wl2[ks], b, acc);
       acc = H16<DT>::mfma(wl[ks], b, acc);
       acc = H16<DT>::mfma(wh[ks], b, acc);
     }

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(256) void sort_keygen_kernel(const float* __restric
   float s = score[b * N + i];
   if (apply_sigmoid) s = 1.0f / (1.0f + expf(-s));
   if (mask) s = s * mask[b * N + i];
+  // -0.0 (a negative score times a zero mask) ties with +0.0, as a compare of values does; on the bits, so that no float rule folds it away
+  if ((__float_as_uint(s) << 1) == 0u) s = 0.f;
   keys[b * ws_stride + i] = desc_key(s);
   idx[b * ws_stride + i] = (unsigned)i;
 }
