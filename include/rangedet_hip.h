@@ -528,8 +528,10 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * down-sampling BasicBlock: weight gradient rd_conv3x3_bwd_weight_ex, data gradient rd_deconv2d_bn_act_all on the weight read as a (3,4)
  * transposed-conv weight with a zero fourth column; its strided 1x1 shortcut runs the 1x1 calls on the pixel-pair view (channel stride
  * 2 cin).  The network's own transposed convs: rd_deconv_bwd_weight and the packers declared with it.  The Meta-Kernel unit
- * with the folded normalisation: rd_meta_kernel_bwd_data and rd_meta_kernel_bwd_params, at the end of this section.  Not here: the concat
- * conv, and the batch-statistics form of the Meta-Kernel's 576-channel BatchNorm.
+ * with the folded normalisation: rd_meta_kernel_bwd_data and rd_meta_kernel_bwd_params, at the end of this section.  The convs that read the
+ * range image itself (res1_unit1's conv1 and projection, the level-0 concat conv): rd_conv_bwd_weight_narrow and
+ * rd_conv3x3_bwd_weight_cat below, their device packers with the optimizer's.  Not here: the batch-statistics form of the Meta-Kernel's
+ * 576-channel BatchNorm, and a device re-pack of that unit.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -561,6 +563,40 @@ int rd_conv3x3_bwd_weight_ex(const void* x, int x_cstride, int x_coff, const voi
                              int Win, int cin, int cout, int stride_w, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H,
                           int W, int cin, int cout, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* The weight gradient of the convs that read the range image itself: res1_unit1's conv1 (c -> 64, ksize 3) and projection shortcut
+ * (c -> 64, ksize 1), and the range-image columns of the level-0 conv_0 (64 + c -> 128); c = 8 (Waymo) or 5 (KITTI).
+ *   dW[co, dw_cin_off + ci, ky, kx] = sum_{b,h,w} dz[b,h,w,co] x[b,h+ky-p,w+kx-p,ci]     ksize 3: p = 1, x zero outside the image; ksize 1: p = 0
+ * float32, stride 1.  dW is laid out (cout, dw_cin_stride, ksize, ksize); only channels [dw_cin_off, dw_cin_off + cin) are written, every
+ * other element is left untouched.  cin 1..16, cout 64 or 128, ksize 1 or 3 (else RD_ESHAPE).  The kernel reads one 16-channel slot per
+ * pixel, exactly as the forward does: x_coff % 8 == 0, x_cstride % 8 == 0, x_coff + 16 <= x_cstride; slot channels at or above cin may
+ * hold any finite values, they reach no written element.  16-bit types only (else RD_EINVAL).
+ * A different kernel from rd_conv3x3_bwd_weight (csrc/k_convbwd_narrow.h): a workgroup owns all of cout x (taps x slot) and a contiguous
+ * run of (frame, 16-row strip, 64-pixel tile) chunks, so dz is read once and x once plus the halo rows of a strip; v_mfma_f32_16x16x32 with
+ * one tap's slot as one N tile, fp32 accumulation over the pixel axis.  The reduction has rd_conv3x3_bwd_weight's contract: split is the
+ * most partial sums per element (0: the library's choice, min(512, chunks)), partial images (split x ksize^2 x cout x cin floats at most)
+ * go to the workspace and a second launch adds them in index order; no atomics, two calls give the same bytes, the bytes do not depend
+ * on the CU count; RD_EWORKSPACE when ws_bytes is too small; the contents of ws on entry do not matter. */
+size_t rd_conv_bwd_weight_narrow_workspace_bytes(int B, int H, int W, int cin, int cout, int ksize, int split);
+int rd_conv_bwd_weight_narrow(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride,
+                              int dw_cin_off, int B, int H, int W, int cin, int cout, int ksize, int split, int dtype, void* ws, size_t ws_bytes,
+                              void* stream);
+/* The weight gradient of the concat conv of rd_conv3x3_bn_act_cat: dW (cout, cin1 + cin2, 3, 3), cin1 64, cin2 1..16, cout 64 or 128 (else
+ * RD_ESHAPE).  Channels [0, cin1) are bit for bit what rd_conv3x3_bwd_weight returns for (x1, dz) with the same split -- the same kernel,
+ * its reduce writing at the channel stride -- and channels [cin1, cin1 + cin2) bit for bit what rd_conv_bwd_weight_narrow returns for
+ * (x2, dz) with ksize 3; x2 is read as a 16-channel slot (x2_coff + 16 <= x2_cstride).  The workspace holds the partial images of both.
+ * The data gradient towards x1 is the persistent forward launch on the flipped image of w[:, :cin1] (rd_pack_conv3x3_ex_host(flip(w[:,
+ * :cin1]), NULL, cin1, cout, 1, cout, dtype)); the range image takes no gradient. */
+size_t rd_conv3x3_bwd_weight_cat_workspace_bytes(int B, int H, int W, int cin1, int cin2, int cout, int split);
+int rd_conv3x3_bwd_weight_cat(const void* x1, int x1_cstride, int x1_coff, int cin1, const void* x2, int x2_cstride, int x2_coff, int cin2,
+                              const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H, int W, int cout, int split, int dtype,
+                              void* ws, size_t ws_bytes, void* stream);
+/* rd_conv3x3_bwd_weight_cat into a gradient laid out (cout, dw_cin_stride, 3, 3) with dw_cin_stride >= cin1 + cin2 (else RD_ESHAPE): the
+ * same bits in channels [0, cin1 + cin2), channels [cin1 + cin2, dw_cin_stride) are never written.  For a master kept at the width the
+ * concat forward reads (cin2 rounded up to 8: KITTI's c = 5 in 8), whose zero padding columns then keep a zero gradient.  The workspace is
+ * that of rd_conv3x3_bwd_weight_cat. */
+int rd_conv3x3_bwd_weight_cat_padded(const void* x1, int x1_cstride, int x1_coff, int cin1, const void* x2, int x2_cstride, int x2_coff, int cin2,
+                                     const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride, int B, int H, int W, int cout,
+                                     int split, int dtype, void* ws, size_t ws_bytes, void* stream);
 /* The backward of the network's transposed convs (the `agg` stages of the DLA backbone: Deconvolution -> BatchNorm -> ReLU -> add(skip, .)).
  * x (B, H, Win, cin), W (cin, cout, 3, kw) in MXNet's Deconvolution layout, stride (1, s), pad (1, p) with kw - 2 p == s, so Wout = s Win;
  * dz is the gradient at the output, (B, H, s Win, cout).  The two forms (kw, s, p) = (4, 2, 1) and (8, 4, 2) at the channel pairs of the
@@ -762,6 +798,20 @@ int rd_sgd_mom_update(const void* table_dev, const void* table_host, float lr, f
 /* One image of a device-resident (cout, cin, 3, 3) float32 weight, cin, cout in {64, 128}: flip == 0 the forward image (fold_scale_dev
  * or NULL), flip != 0 the data-gradient image (fold_scale_dev must be NULL).  One launch, the zero tail included. */
 int rd_pack_conv3x3_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin, int flip, int dtype, void* out_dev, void* stream);
+/* The launch images of the convs that read the range image, from device-resident float32 masters: one launch each, the zero fill behind
+ * the weights and the zero tail included; byte for byte the host packers' images:
+ *   rd_pack_conv_narrow_dev, ksize 3    rd_pack_conv3x3_ex_host(w, s, cout, cin, 1, cin, dtype), the <= 16-channel body form (cin 1..16)
+ *   rd_pack_conv_narrow_dev, ksize 1    rd_pack_conv_weight_host(w, cout, cin, 1, 1, dtype); fold_scale_dev must be NULL (else RD_EINVAL)
+ *   rd_pack_conv3x3_cat_dev, data_grad 0   rd_pack_conv3x3_cat_host(w, s, cout, cin1, cin2, dtype); w (cout, cin1 + cin2, 3, 3), cin1 64, cin2 a
+ *                                          multiple of 8 as the forward requires (else RD_ESHAPE)
+ *   rd_pack_conv3x3_cat_dev, data_grad 1   rd_pack_conv3x3_ex_host(flip(w[:, :cin1]), NULL, cin1, cout, 1, cout, dtype), the image of the data
+ *                                          gradient towards x1 (cin2 1..16 only sets the master's channel stride); fold_scale_dev must be NULL
+ * A trap in the host packers: they choose the <= 16-channel and the concat body layouts only when they are given a fold scale, while the
+ * forward launches always read those layouts under RD_SCALE_FOLDED.  The unscaled training image is therefore the host packer called with a
+ * fold scale of ONES (the product by 1.0f is exact), and these two calls take fold_scale_dev == NULL to mean exactly that. */
+int rd_pack_conv_narrow_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin, int ksize, int dtype, void* out_dev, void* stream);
+int rd_pack_conv3x3_cat_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin1, int cin2, int data_grad, int dtype,
+                            void* out_dev, void* stream);
 
 /* ---- per-kernel timing (HIP events on the launch stream; used by bench.py's roofline block) --------- */
 #define RD_PROF_CONV 0

@@ -27,8 +27,8 @@ parameter the way the towers do: rangedet_amd.optim.SGD.attach(block) registers 
 weights.  Refused with NotImplementedError: fewer than 64 input channels (res1_unit1), the Meta-Kernel unit, channel counts outside
 {64, 128}, an identity shortcut between different channel counts, a strided unit handed to BasicBlockTrain.
 AggStageTrain is a whole `agg` stage -- the transposed conv, its BatchNorm and ReLU, the add of the skip, then a ResStageTrain -- forward
-and backward (its docstring has the steps), so the gradient of the head levels reaches the `res` stages below.  Still without a backward:
-the level-0 concat conv and the Meta-Kernel unit.
+and backward (its docstring has the steps), so the gradient of the head levels reaches the `res` stages below.  StemBlockTrain is res1_unit1, the block that reads
+the range image itself (1 .. 16 input channels in the 16-channel slot; no dx).
 """
 import numpy as np
 
@@ -257,6 +257,96 @@ class BasicBlockTrain(_BlockTrain):
             raise NotImplementedError("%s: an identity shortcut from %d to %d channels -- different channel counts need the projection "
                                       "(sc_w, sc_bn)" % (name, cin, cout))
         self._build(name, w1, w2, cin, cout, bn1, bn2, sc_w, sc_bn, dtype, eps, momentum, lib, alloc)
+
+
+class StemBlockTrain(_BlockTrain):
+    """res1_unit1 as the reference trains it: the BasicBlock that reads the range image itself, c -> 64 with the projection shortcut.  The
+    constructor, aux(), the gradient names and optimizer_entries() are BasicBlockTrain's; c = conv1_w.shape[1] is 1 .. 16 (8 for Waymo, 5
+    for KITTI) and x is the (B, H, W, 16) range-image slot, of which only the first c channels meet a non-zero weight.
+
+        forward   z1 = conv3x3(x, W1)          conv_unscaled on the <= 16-channel body form (pack_narrow), x_cs = 16
+                  y1, z2, zs, y                 as in BasicBlockTrain; zs = conv1x1(x, Ws) on the slot
+        backward  dz2, dr, ... = bn_add_relu_bwd(g, z2, zs);  dW2 = weight_grad(y1, dz2);  g1 = data_grad(dz2, W2)
+                  dz1, ... = bn_relu_bwd(g1, z1)
+                  dW1 = weight_grad_narrow(x, dz1, c, 3);  dWs = weight_grad_narrow(x, dr, c, 1)       rd_conv_bwd_weight_narrow
+                  no dx: the range image takes no gradient, backward(g) returns (None, grads)
+
+    optimizer_entries() names conv1 and the projection with pack=dict(narrow=3 | 1, fwd=...): SGD.step() re-packs their forward images from
+    the masters (rd_pack_conv_narrow_dev); neither has a data-gradient image.  Keeps x, z1, y1, z2, zs, saved, y from forward() and g, dz2,
+    dr, g1, dz1 from backward()."""
+
+    def __init__(self, name, conv1_w, conv2_w, bn1, bn2, sc_w=None, sc_bn=None, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM,
+                 stride=(1, 1), meta_kernel=False, lib=None, alloc=None):
+        if meta_kernel or conv1_w is None or tuple(stride) != (1, 1):
+            raise NotImplementedError("%s: a Meta-Kernel or strided unit -- the stem is the stride-1 BasicBlock on the range image" % name)
+        w1, w2 = np.ascontiguousarray(conv1_w, dtype=np.float32), np.ascontiguousarray(conv2_w, dtype=np.float32)
+        if w1.ndim != 4 or w1.shape[2:] != (3, 3) or w2.shape != (w1.shape[0], w1.shape[0], 3, 3):
+            raise ValueError("%s: conv1 (cout, c, 3, 3) and conv2 (cout, cout, 3, 3), got %r and %r" % (name, w1.shape, w2.shape))
+        cout, c = w1.shape[:2]
+        if not 1 <= c <= 16 or cout != 64:
+            raise NotImplementedError("%s: %d -> %d channels; the stem is 1 .. 16 range-image channels -> 64 (64 or more input channels: "
+                                      "BasicBlockTrain)" % (name, c, cout))
+        if sc_w is None or sc_bn is None:
+            raise NotImplementedError("%s: the stem without a projection -- %d channels cannot be added to %d (sc_w, sc_bn)" % (name, c, cout))
+        ws = np.asarray(sc_w, np.float32)
+        ws = np.ascontiguousarray(ws.reshape(ws.shape[0], -1))
+        if ws.shape != (cout, c):
+            raise ValueError("%s: the projection is a (%d, %d[, 1, 1]) weight, got %r" % (name, cout, c, np.asarray(sc_w).shape))
+        self.name = name
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        self.cin, self.cout, self.proj = c, cout, True
+        self.eps, self.momentum = float(eps), float(momentum)
+        A = o.A
+        self.convs = {"conv1": dict(cin=c, cout=cout, fwd=o.pack_narrow(w1, 3), master=A.upload(w1)),
+                      "conv2": dict(cin=cout, cout=cout, fwd=o.pack_unscaled(w2), bwd=o.pack_data_grad(w2), master=A.upload(w2)),
+                      "sc": dict(cin=c, cout=cout, fwd=o.pack_narrow(ws.reshape(cout, c, 1, 1), 1), master=A.upload(ws))}
+        self.bns = {"bn1": self._bn(bn1, "bn1"), "bn2": self._bn(bn2, "bn2"), "sc_bn": self._bn(sc_bn, "sc_bn")}
+        self.x = self.saved = None
+
+    def forward(self, x, unbiased=True):
+        o, cv, c, C = self.ops, self.convs, self.cin, self.cout
+        if _check16(x, "x")[3] != 16:
+            raise ValueError("%s: %d input channels -- x is the (B, H, W, 16) range-image slot" % (self.name, int(x.shape[3])))
+        saved = {}
+        z1 = o.conv_unscaled(x, cv["conv1"]["fwd"], c, C, tag=1, x_cs=16)
+        saved["bn1"] = self._norm(z1, "bn1", 1, unbiased)
+        y1 = o.affine_relu(z1, saved["bn1"]["a"], saved["bn1"]["b"], tag=1)
+        z2 = o.conv_unscaled(y1, cv["conv2"]["fwd"], C, C, tag=2)
+        saved["bn2"] = self._norm(z2, "bn2", 2, unbiased)
+        zs = o.conv1x1(x, cv["sc"]["fwd"], c, C, ("zs", 0), x_cs=16)
+        saved["sc_bn"] = self._norm(zs, "sc_bn", "s", unbiased)
+        s2, ss = saved["bn2"], saved["sc_bn"]
+        y = o.affine_add_relu(z2, s2["a"], s2["b"], zs, ss["a"], ss["b"])
+        self.x, self.z1, self.y1, self.z2, self.zs, self.saved, self.y = x, z1, y1, z2, zs, saved, y
+        return y
+
+    def backward(self, g):
+        if self.x is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(x)")
+        o, cv, bn, sv, nm = self.ops, self.convs, self.bns, self.saved, self.name
+        grads = {}
+        dz2, dr, grads[nm + "_bn2_gamma"], grads[nm + "_bn2_beta"], grads[nm + "_sc_bn_gamma"], grads[nm + "_sc_bn_beta"] = o.bn_add_relu_bwd(
+            g, self.z2, self.zs, sv["bn2"], bn["bn2"]["gamma"], sv["sc_bn"], bn["sc_bn"]["gamma"], tag=2)
+        grads[nm + "_conv2_weight"] = o.weight_grad(self.y1, dz2, tag=2)
+        g1 = o.data_grad(dz2, cv["conv2"]["bwd"], tag=2)
+        dz1, grads[nm + "_bn1_gamma"], grads[nm + "_bn1_beta"] = o.bn_relu_bwd(g1, self.z1, sv["bn1"], bn["bn1"]["gamma"], tag=1)
+        grads[nm + "_conv1_weight"] = o.weight_grad_narrow(self.x, dz1, self.cin, 3, tag=1)
+        grads[nm + "_sc_weight"] = o.weight_grad_narrow(self.x, dr, self.cin, 1, tag="s")
+        self.g, self.dz2, self.dr, self.g1, self.dz1 = g, dz2, dr, g1, dz1
+        return None, grads
+
+    def optimizer_entries(self):
+        o, nm, c, C = self.ops, self.name, self.cin, self.cout
+        A, cv = o.A, self.convs
+        yield dict(name=nm + "_conv1_weight", weight=A.view_f32(cv["conv1"]["master"], (C, c, 3, 3)),
+                   grad=A.view_f32(o.buf(("dWn", 1), C * c * 36), (C, c, 3, 3)), pack=dict(narrow=3, fwd=cv["conv1"]["fwd"][0], dtype=o.dt))
+        yield from self._norm_entries("bn1", ("bn_dgamma", 1), ("bn_dbeta", 1))
+        yield dict(name=nm + "_conv2_weight", weight=A.view_f32(cv["conv2"]["master"], (C, C, 3, 3)),
+                   grad=A.view_f32(o.buf(("dW", 2), C * C * 36), (C, C, 3, 3)), pack=dict(fwd=cv["conv2"]["fwd"][0], bwd=cv["conv2"]["bwd"][0], dtype=o.dt))
+        yield from self._norm_entries("bn2", ("bn_dgamma", 2), ("bn_dbeta", 2))
+        yield dict(name=nm + "_sc_weight", weight=A.view_f32(cv["sc"]["master"], (C, c, 1, 1)),
+                   grad=A.view_f32(o.buf(("dWn", "s"), C * c * 4), (C, c, 1, 1)), pack=dict(narrow=1, fwd=cv["sc"]["fwd"], dtype=o.dt))
+        yield from self._norm_entries("sc_bn", ("bn_dgamma_r", 2), ("bn_dbeta_r", 2))
 
 
 class DownBlockTrain(_BlockTrain):

@@ -18,7 +18,8 @@ so a result is valid until the next such call.  TowerOps holds the single steps,
 conv launch: the towers' forward, the unscaled conv and the data gradient all go through it).  _HeadTower is the skeleton both towers
 share -- the layer checks, the parameter names, the output conv, the forward and backward loops; a tower adds its layer parameters, one
 layer's forward and the step from dL/dy to dz.  HeadTowerBackward is the tower with inference-mode normalisation (fixed folded s and t);
-the level-0 conv_0 (input: the un-materialised 64 + 8 channel concat) and strided / transposed convs are refused.
+the level-0 conv_0 (input: the un-materialised 64 + 8 channel concat) and strided / transposed convs are refused there; Level0TowerTrain
+is the training-mode tower whose first layer is that concat conv.
 
 HeadTowerTrain is the tower as the reference trains it (normalizer_factory(type="localbn"), mxnext/complicate.py:26-45: BatchNorm with the
 batch's own statistics after every conv).  With z = conv3x3(x, W) rounded to the activation type, n = B H W, float32 (csrc/k_norm.h):
@@ -104,12 +105,13 @@ class TowerOps:
         wf = np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1])
         return self.A.upload(self.L.pack_conv3x3_ex(wf, 1, cout, fold_scale=None, dtype=self.dt)), self.A.upload(np.zeros(cin, np.float32)), cin
 
-    def conv3x3(self, x, image, shift, cin, cout, flags, key):
-        """the persistent forward launch: x (B, H, W, cin) -> (B, H, W, cout) in the buffer `key`; image a packed weight, shift cout float32"""
+    def conv3x3(self, x, image, shift, cin, cout, flags, key, x_cs=None):
+        """the persistent forward launch: x (B, H, W, cin) -> (B, H, W, cout) in the buffer `key`; image a packed weight, shift cout float32.
+        x_cs: the channel stride of x when it is wider than cin (the 16-channel range-image slot)"""
         A = self.A
         B, H, W = _check16(x, "x")[:3]
         out = self.buf(key, B * H * W * cout * 2)
-        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), cin, 0, A.ptr(image), None, A.ptr(shift), None, 0, 0, None, 0, 0, 0, None,
+        self.L.call("rd_conv3x3_bn_act_ex", rdlib.ptr(x), x_cs or cin, 0, A.ptr(image), None, A.ptr(shift), None, 0, 0, None, 0, 0, 0, None,
                     A.ptr(out), cout, 0, B, H, W, cin, cout, 1, flags, self.dt, _stream(A))
         return _view16(A, out, (B, H, W, cout), self.dt)
 
@@ -142,6 +144,96 @@ class TowerOps:
                nws, _stream(A))
         return A.view_f32(out, (cout, cin, 3, 3))
 
+    def weight_grad_narrow(self, x, dz, cin, ksize, tag=0, split=0):
+        """x (B, H, W, 16): the range-image slot, of which the first cin channels are the conv's input; dz (B, H, W, cout) -> dW (cout, cin,
+        ksize, ksize) float32 (rd_conv_bwd_weight_narrow: ksize 3 pad 1, or ksize 1)"""
+        A, L = self.A, self.L
+        B, H, W, slot = _check16(x, "x")
+        if _check16(dz, "dz")[:3] != (B, H, W):
+            raise ValueError("weight_grad_narrow: x %r and dz %r differ in B, H or W" % (tuple(x.shape), tuple(dz.shape)))
+        cout = int(dz.shape[3])
+        if slot != 16 or not 1 <= cin <= 16 or cout not in (64, 128) or ksize not in (1, 3):
+            raise NotImplementedError("weight_grad_narrow: %d of %d slot channels -> %d, ksize %r; the kernel reads a 16-channel slot with 1 .. 16 "
+                                      "input channels, 64 or 128 output channels, ksize 1 or 3" % (cin, slot, cout, ksize))
+        nws = L.raw("rd_conv_bwd_weight_narrow_workspace_bytes")(B, H, W, cin, cout, ksize, split)
+        ws, out = self.buf(("bwn_ws", 0), nws), self.buf(("dWn", tag), cout * cin * ksize * ksize * 4)
+        L.call("rd_conv_bwd_weight_narrow", rdlib.ptr(x), 16, 0, rdlib.ptr(dz), cout, 0, A.ptr(out), cin, 0, B, H, W, cin, cout, ksize, split, self.dt,
+               A.ptr(ws), nws, _stream(A))
+        return A.view_f32(out, (cout, cin, ksize, ksize))
+
+    def weight_grad_cat(self, x1, x2, cin2, dz, tag=0, split=0, cin_stride=None):
+        """the concat conv [x1 | first cin2 channels of x2] -> cout: x1 (B, H, W, 64), x2 (B, H, W, 16) the range-image slot, dz (B, H, W, cout)
+        -> dW (cout, 64 + cin2, 3, 3) float32 (rd_conv3x3_bwd_weight_cat).  cin_stride > 64 + cin2: dW is (cout, cin_stride, 3, 3), a buffer
+        zeroed when it is made whose channels from 64 + cin2 on no launch writes (rd_conv3x3_bwd_weight_cat_padded)"""
+        A, L = self.A, self.L
+        B, H, W, cin1 = _check16(x1, "x1")
+        if _check16(x2, "x2")[:3] != (B, H, W) or _check16(dz, "dz")[:3] != (B, H, W):
+            raise ValueError("weight_grad_cat: x1 %r, x2 %r and dz %r differ in B, H or W" % (tuple(x1.shape), tuple(x2.shape), tuple(dz.shape)))
+        cout = int(dz.shape[3])
+        if cin1 != 64 or int(x2.shape[3]) != 16 or not 1 <= cin2 <= 16 or cout not in (64, 128):
+            raise NotImplementedError("weight_grad_cat: %d + %d of %d slot channels -> %d; 64 + (1 .. 16 of a 16-channel slot) -> 64 or 128"
+                                      % (cin1, cin2, int(x2.shape[3]), cout))
+        nws = L.raw("rd_conv3x3_bwd_weight_cat_workspace_bytes")(B, H, W, cin1, cin2, cout, split)
+        cs = cin_stride or cin1 + cin2
+        if cs < cin1 + cin2:
+            raise ValueError("weight_grad_cat: cin_stride %d below %d + %d channels" % (cs, cin1, cin2))
+        ws, out = self.buf(("bwc_ws", 0), nws), self.buf(("dWc", tag), cout * cs * 36, zero=True)
+        if cs == cin1 + cin2:
+            L.call("rd_conv3x3_bwd_weight_cat", rdlib.ptr(x1), cin1, 0, cin1, rdlib.ptr(x2), 16, 0, cin2, rdlib.ptr(dz), cout, 0, A.ptr(out), B, H, W,
+                   cout, split, self.dt, A.ptr(ws), nws, _stream(A))
+        else:
+            L.call("rd_conv3x3_bwd_weight_cat_padded", rdlib.ptr(x1), cin1, 0, cin1, rdlib.ptr(x2), 16, 0, cin2, rdlib.ptr(dz), cout, 0, A.ptr(out), cs,
+                   B, H, W, cout, split, self.dt, A.ptr(ws), nws, _stream(A))
+        return A.view_f32(out, (cout, cs, 3, 3))
+
+    # The launch images of these convs.  The forward launches read the <= 16-channel and the concat body forms, which the host packers write
+    # only when they are given a fold scale: the unscaled training image is packed with a vector of ones (1.0f * w is w), and the device
+    # packers take fold = None to mean exactly that.
+    def pack_narrow(self, w, ksize):
+        """(cout, cin, ksize, ksize), cin <= 16 -> ksize 3: (image, zero shift) for conv_unscaled(x, ., cin, cout, x_cs=16); ksize 1: the
+        image conv1x1(x, ., cin, cout, key, x_cs=16) reads"""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        cout, cin = w.shape[:2]
+        if w.shape[2:] != (ksize, ksize) or ksize not in (1, 3) or not 1 <= cin <= 16 or cout not in (64, 128):
+            raise NotImplementedError("pack_narrow: a (cout, cin, %r, %r) weight with ksize 1 or 3, cin 1 .. 16, cout 64 or 128, got %r" % (ksize, ksize, w.shape))
+        if ksize == 1:
+            return self.pack_conv1x1(w)
+        image = self.L.pack_conv3x3_ex(w, 1, cin, fold_scale=np.ones(cout, np.float32), dtype=self.dt)
+        return self.A.upload(image), self.A.upload(np.zeros(cout, np.float32))
+
+    def pack_narrow_dev(self, master, cout, cin, ksize, image, fold_scale=None):
+        """the same image from the device-resident float32 master, one launch (rd_pack_conv_narrow_dev)"""
+        self.L.call("rd_pack_conv_narrow_dev", rdlib.ptr(master), None if fold_scale is None else rdlib.ptr(fold_scale), cout, cin, ksize, self.dt,
+                    rdlib.ptr(image), _stream(self.A))
+
+    def pack_cat(self, w, cin2):
+        """(cout, 64 + cin2, 3, 3), cin2 8 or 16 -> (image, zero shift) of the unscaled concat conv (conv3x3_cat)"""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        cout = w.shape[0]
+        if w.shape[1:] != (64 + cin2, 3, 3) or cin2 not in (8, 16) or cout not in (64, 128):
+            raise NotImplementedError("pack_cat: a (cout, 64 + cin2, 3, 3) weight with cin2 8 or 16 (the forward reads a multiple of 8) and cout 64 "
+                                      "or 128, got %r with cin2 %r" % (w.shape, cin2))
+        image = self.L.pack_conv3x3_cat(w, 64, cin2, fold_scale=np.ones(cout, np.float32), dtype=self.dt)
+        return self.A.upload(image), self.A.upload(np.zeros(cout, np.float32))
+
+    def pack_cat_dev(self, master, cout, cin2, data_grad, image, fold_scale=None):
+        """the forward image (data_grad False) or the image of the data gradient towards x1 (True) of the concat conv from the device-resident
+        (cout, 64 + cin2, 3, 3) master, one launch (rd_pack_conv3x3_cat_dev)"""
+        self.L.call("rd_pack_conv3x3_cat_dev", rdlib.ptr(master), None if fold_scale is None else rdlib.ptr(fold_scale), cout, 64, cin2,
+                    1 if data_grad else 0, self.dt, rdlib.ptr(image), _stream(self.A))
+
+    def conv3x3_cat(self, x1, x2, cin2, packed, cout, tag=0):
+        """z = conv3x3([x1 | first cin2 channels of x2], W) rounded to the activation type, unscaled (rd_conv3x3_bn_act_cat on the never-written
+        concat): x1 (B, H, W, 64), x2 (B, H, W, 16) the range-image slot, cin2 8 or 16, packed = pack_cat(W, cin2)"""
+        A = self.A
+        B, H, W, cin1 = _check16(x1, "x1")
+        if _check16(x2, "x2") != (B, H, W, 16) or cin1 != 64 or cin2 not in (8, 16):
+            raise NotImplementedError("conv3x3_cat: x1 %r, x2 %r, cin2 %r -- (B, H, W, 64), the (B, H, W, 16) slot, 8 or 16" % (tuple(x1.shape), tuple(x2.shape), cin2))
+        out = self.buf(("z", tag), B * H * W * cout * 2)
+        self.L.call("rd_conv3x3_bn_act_cat", rdlib.ptr(x1), cin1, 0, cin1, rdlib.ptr(x2), 16, 0, cin2, A.ptr(packed[0]), A.ptr(packed[1]), A.ptr(out),
+                    cout, 0, B, H, W, cout, rdlib.RD_SCALE_FOLDED, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, cout), self.dt)
+
     def relu_affine_bwd(self, g, y, scale, tag=0):
         """g, y (B, H, W, C), scale a device float32 buffer of C values or None -> dz"""
         A, L = self.A, self.L
@@ -170,10 +262,10 @@ class TowerOps:
         return _view16(A, dx, (B, H, W, cin), self.dt), A.view_f32(dw, (nout, cin)), A.view_f32(db, (nout,))
 
     # ---- training-mode batch norm (csrc/k_norm.h); every vector below is a device buffer of C float32 values ------------------------------
-    def conv_unscaled(self, x, packed, cin, cout, tag=0):
+    def conv_unscaled(self, x, packed, cin, cout, tag=0, x_cs=None):
         """z = conv3x3(x, W) rounded to the activation type: the persistent launch on an unscaled weight image, zero shift, no activation;
-        packed = (image, zero shift) as pack_unscaled makes them"""
-        return self.conv3x3(x, packed[0], packed[1], cin, cout, rdlib.RD_SCALE_FOLDED, ("z", tag))
+        packed = (image, zero shift) as pack_unscaled (or, for at most 16 input channels in a slot of x_cs, pack_narrow) makes them"""
+        return self.conv3x3(x, packed[0], packed[1], cin, cout, rdlib.RD_SCALE_FOLDED, ("z", tag), x_cs)
 
     def pack_unscaled(self, w_oihw):
         w = np.asarray(w_oihw, np.float32)
@@ -260,20 +352,21 @@ class TowerOps:
         w = np.ascontiguousarray(np.asarray(w_oi, np.float32).reshape(w_oi.shape[0], -1))
         return self.A.upload(self.L.pack_conv_weight(w.reshape(w.shape + (1, 1)), self.dt))
 
-    def conv1x1(self, x, image, cin, cout, key, pair=None):
+    def conv1x1(self, x, image, cin, cout, key, pair=None, x_cs=None):
         """x (B, H, W, cin) -> conv1x1(x, W) rounded to the activation type, in the buffer `key`; image = pack_conv1x1(W).  With the image of
         the transposed weight this is the 1x1 conv's data gradient.  The stride-(1,2) 1x1 conv runs the same launch on the pixel-pair view,
         a row of W pixels read as W / 2 pixels of twice the channel stride whose first cin (cout) channels are the even pixel:
           pair='in'    x (B, H, W, cin), W even -> (B, H, W / 2, cout): the conv of the even pixels, the strided forward
           pair='out'   x (B, H, Wo, cin) -> (B, H, 2 Wo, cout): the result on the even pixels, +0 on the odd ones (the buffer is zeroed when
-                       it is made and its odd pixels are never written), the strided conv's data gradient"""
+                       it is made and its odd pixels are never written), the strided conv's data gradient
+        x_cs: the channel stride of x when it is wider than cin (the 16-channel range-image slot)"""
         A = self.A
         B, H, W = _check16(x, "x")[:3]
         if pair not in (None, "in", "out") or (pair == "in" and W % 2):
             raise NotImplementedError("conv1x1: pair %r with W %d -- None, 'in' with an even width, or 'out'" % (pair, W))
         Wl, Wout = (W // 2, W // 2) if pair == "in" else (W, 2 * W if pair == "out" else W)
         out = self.buf(key, B * H * Wout * cout * 2, zero=pair == "out")
-        self.L.call("rd_conv2d_bn_act", rdlib.ptr(x), cin * (2 if pair == "in" else 1), 0, A.ptr(image), None, None, None, 0, 0, A.ptr(out),
+        self.L.call("rd_conv2d_bn_act", rdlib.ptr(x), (x_cs or cin) * (2 if pair == "in" else 1), 0, A.ptr(image), None, None, None, 0, 0, A.ptr(out),
                     cout * (2 if pair == "out" else 1), 0, B, H, Wl, cin, cout, 1, 1, 1, 0, self.dt, _stream(A))
         return _view16(A, out, (B, H, Wout, cout), self.dt)
 
@@ -661,17 +754,12 @@ class _HeadTower:
             name = "rpn_%s_conv_%d_lvl_%d" % (kind, first_conv + i, level)
             if w.ndim != 4 or w.shape[2:] != (3, 3):
                 raise NotImplementedError("%s: kernel %r -- 3x3, stride 1, pad 1 only (no strided or transposed conv)" % (name, w.shape[2:]))
-            cout, cin = w.shape[:2]
-            if cin not in (64, 128) or cout not in (64, 128):
-                why = " (the level-0 conv_0 reads the un-materialised concat of 64 + 8 channels: the concat conv has no backward here)" \
-                    if cin == 72 else ""
-                raise NotImplementedError("%s: %d -> %d channels; the backward kernels run 64 or 128 on either side%s" % (name, cin, cout, why))
+            cout, cin = self._layer_channels(i, w, name)
             if chans is not None and cin != chans:
                 raise ValueError("%s: %d input channels after a layer with %d outputs" % (name, cin, chans))
             chans = cout
             self._stems.append(name)
-            self.layers.append(dict(self._layer(w, name, *(p[i] for p in params)), cin=cin, cout=cout, bwd=o.pack_data_grad(w),
-                                    master=o.A.upload(np.ascontiguousarray(w))))
+            self.layers.append(dict(self._layer(w, name, *(p[i] for p in params)), cin=cin, cout=cout, **self._weight_images(i, w)))
         ow = np.asarray(out_weight, np.float32)
         ow = np.ascontiguousarray(ow.reshape(ow.shape[0], -1))
         ob = np.ascontiguousarray(out_bias, dtype=np.float32)
@@ -685,6 +773,26 @@ class _HeadTower:
         self.out_w, self.out_b = o.A.upload(ow), o.A.upload(ob)
         self.acts = None
 
+    def _layer_channels(self, i, w, name):
+        """the channel check of layer i -> (cout, cin as the tower's input sees it)"""
+        cout, cin = w.shape[:2]
+        if cin not in (64, 128) or cout not in (64, 128):
+            why = " (the level-0 conv_0 reads the un-materialised concat of 64 + 8 channels: the concat conv has no backward here)" \
+                if cin == 72 else ""
+            raise NotImplementedError("%s: %d -> %d channels; the backward kernels run 64 or 128 on either side%s" % (name, cin, cout, why))
+        return cout, cin
+
+    def _weight_images(self, i, w):
+        """layer i's data-gradient image and float32 master (a subclass whose layer has other images overrides this and _layer)"""
+        return dict(bwd=self.ops.pack_data_grad(w), master=self.ops.A.upload(np.ascontiguousarray(w)))
+
+    def _weight_entry(self, i, stem, ly):
+        """SGD.add's arguments for layer i's conv weight"""
+        o = self.ops
+        shape = (ly["cout"], ly["cin"], 3, 3)
+        return dict(name=stem + "_weight", weight=o.A.view_f32(ly["master"], shape), grad=o.A.view_f32(o.buf(("dW", i), ly["cout"] * ly["cin"] * 36), shape),
+                    pack=dict(self._fwd_image(ly), bwd=ly["bwd"][0], dtype=o.dt))
+
     def optimizer_entries(self):
         """What rangedet_amd.optim.SGD.attach registers, one dict of SGD.add's arguments per trainable parameter: its reference name, the
         float32 master weight and the gradient buffer backward() fills (the buffers TowerOps keys by step and layer: their addresses do not
@@ -693,9 +801,7 @@ class _HeadTower:
         o = self.ops
         A, n = o.A, len(self.layers)
         for i, (stem, ly) in enumerate(zip(self._stems, self.layers)):
-            shape = (ly["cout"], ly["cin"], 3, 3)
-            yield dict(name=stem + "_weight", weight=A.view_f32(ly["master"], shape), grad=A.view_f32(o.buf(("dW", i), ly["cout"] * ly["cin"] * 36), shape),
-                       pack=dict(self._fwd_image(ly), bwd=ly["bwd"][0], dtype=o.dt))
+            yield self._weight_entry(i, stem, ly)
             yield from self._norm_entries(i, stem, ly)
         cin = self.layers[n - 1]["cout"]
         yield dict(name=self.out_names[0], weight=A.view_f32(self.out_w, (self.nout, cin, 1, 1)),
@@ -717,6 +823,9 @@ class _HeadTower:
         self.acts = acts
         return A.view_f32(out, (B, H * W, self.nout))
 
+    def _weight_grad(self, i, x, dz):
+        return self.ops.weight_grad(x, dz, tag=i)
+
     def backward(self, d_out, n_off=0, out_batch_stride=None):
         """d_out: the float32 gradient of the head output, the level at pixel offset n_off of each frame's run -- RpnLoss's flat d_logit
         (B, N) / d_delta (B, N, 8) are read in place.  -> (the gradient of the tower input in the activation type, {reference parameter
@@ -730,7 +839,7 @@ class _HeadTower:
         for i in range(n - 1, -1, -1):
             gs[i] = g
             dzs[i] = self._dz(i, g, grads)
-            grads[self._stems[i] + "_weight"] = o.weight_grad(acts[i], dzs[i], tag=i)
+            grads[self._stems[i] + "_weight"] = self._weight_grad(i, acts[i], dzs[i])
             g = dxs[i] = o.data_grad(dzs[i], self.layers[i]["bwd"], tag=i)
         self.gs, self.dzs, self.dxs = gs, dzs, dxs
         return g, grads
@@ -838,3 +947,88 @@ class HeadTowerBackward(_HeadTower):
         if i == len(self.layers) - 1:
             return g
         return self.ops.relu_affine_bwd(g, self.acts[i + 1], self.layers[i]["scale"], tag=i)
+
+
+class Level0TowerTrain(HeadTowerTrain):
+    """The level-0 tower as the reference trains it: a HeadTowerTrain whose first layer is the concat conv rpn_{cls,reg}_conv_0_lvl_0 on
+    [agg3 | range image] (dla_backbone.py:153-154), the concat never written: conv_weights[0] is (cout, 64 + c, 3, 3) with c the range
+    image's channels (8 for Waymo, 5 for KITTI; 1 .. 16), the other layers 128 -> 128.
+      forward(x, data) -> the head output; x (B, H, W, 64) the agg3 feature map, data (B, H, W, 16) the range-image slot
+                          conv3x3_cat (rd_conv3x3_bn_act_cat, unscaled), then as the tower
+      backward(d_out, n_off) -> (the gradient of x, grads): layer 0's weight gradient is weight_grad_cat in the reference's shape
+                          (cout, 64 + c, 3, 3), its data gradient towards x the persistent launch on the flipped image of w[:, :64]; the
+                          range image takes no gradient
+    The concat forward reads a multiple of 8 range-image channels, so the device master is kept at that width, (cout, 64 + c8, 3, 3) with
+    c8 = c rounded up to 8 and the columns from 64 + c on zero.  They stay exactly zero through any number of steps: the gradient buffer
+    has the master's layout, is zeroed once when it is made, and rd_conv3x3_bwd_weight_cat_padded never writes those columns, so their
+    update is momentum * 0 - lr wd * 0 - lr * 0.  With c a multiple of 8 there is no padding.  Slot channels c .. c8 - 1 of `data` meet
+    only those zero weights.  The returned gradient is the (cout, 64 + c, 3, 3) view of that buffer.
+    optimizer_entries() names the concat weight with pack=dict(cat=(64, c8), ...): SGD.step() re-packs both images from the master."""
+
+    def __init__(self, conv_weights, gammas, betas, moving_means, moving_vars, out_weight, out_bias, kind="cls", level=0, first_conv=0,
+                 eps=BN_EPS, momentum=BN_MOMENTUM, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        super().__init__(conv_weights, gammas, betas, moving_means, moving_vars, out_weight, out_bias, kind, level, first_conv, eps, momentum,
+                         dtype, lib, alloc)
+        self.data = None
+
+    def _layer_channels(self, i, w, name):
+        if i:
+            return super()._layer_channels(i, w, name)
+        if w.shape[0] not in (64, 128) or not 64 < w.shape[1] <= 80:
+            raise NotImplementedError("%s: %r -- the concat conv is a (cout, 64 + c, 3, 3) weight, c 1 .. 16" % (name, w.shape))
+        self.c = int(w.shape[1]) - 64
+        self.c8 = (self.c + 7) // 8 * 8
+        return int(w.shape[0]), 64              # the tower's input x is the 64-channel half
+
+    def _layer(self, w, name, gamma, beta, mmean, mvar):
+        if self.layers:
+            return super()._layer(w, name, gamma, beta, mmean, mvar)
+        return self._layer0(w, name, gamma, beta, mmean, mvar)
+
+    def _layer0(self, w, name, gamma, beta, mmean, mvar):
+        o, cout = self.ops, w.shape[0]
+        return dict(fwd=o.pack_cat(self._padded(w), self.c8), gamma=_vec(o, gamma, cout, name + "_bn_gamma"), beta=_vec(o, beta, cout, name + "_bn_beta"),
+                    mmean=_vec(o, mmean, cout, name + "_bn_moving_mean"), mvar=_vec(o, mvar, cout, name + "_bn_moving_var"))
+
+    def _padded(self, w):
+        wp = np.zeros((w.shape[0], 64 + self.c8, 3, 3), np.float32)
+        wp[:, :64 + self.c] = w
+        return wp
+
+    def _weight_images(self, i, w):
+        if i:
+            return super()._weight_images(i, w)
+        o = self.ops
+        return dict(bwd=o.pack_data_grad(np.ascontiguousarray(w[:, :64])), master=o.A.upload(self._padded(w)))
+
+    def _weight_entry(self, i, stem, ly):
+        if i:
+            return super()._weight_entry(i, stem, ly)
+        o = self.ops
+        shape = (ly["cout"], 64 + self.c8, 3, 3)
+        return dict(name=stem + "_weight", weight=o.A.view_f32(ly["master"], shape),
+                    grad=o.A.view_f32(o.buf(("dWc", 0), ly["cout"] * (64 + self.c8) * 36, zero=True), shape),
+                    pack=dict(cat=(64, self.c8), fwd=ly["fwd"][0], bwd=ly["bwd"][0], dtype=o.dt))
+
+    def forward(self, x, data, unbiased=True):
+        if _check16(data, "data") != tuple(int(v) for v in x.shape[:3]) + (16,):
+            raise ValueError("forward: data %r with x %r -- the (B, H, W, 16) range-image slot" % (tuple(data.shape), tuple(x.shape)))
+        self.data = data
+        return super().forward(x, unbiased)
+
+    def _layer_forward(self, i, x):
+        if i:
+            return super()._layer_forward(i, x)
+        o, ly = self.ops, self.layers[0]
+        z = o.conv3x3_cat(x, self.data, self.c8, ly["fwd"], ly["cout"], tag=0)
+        mean, var = o.bn_stats(z, tag=0)
+        rstd, a, b = o.bn_fold(mean, var, ly["gamma"], ly["beta"], ly["mmean"], ly["mvar"], int(np.prod(z.shape[:3])), ly["cout"], self.eps,
+                               self.momentum, self._unbiased, tag=0)
+        self.zs.append(z)
+        self.saved.append(dict(a=a, b=b, mean=mean, var=var, rstd=rstd))
+        return o.affine_relu(z, a, b, tag=0)
+
+    def _weight_grad(self, i, x, dz):
+        if i:
+            return super()._weight_grad(i, x, dz)
+        return self.ops.weight_grad_cat(x, self.data, self.c, dz, tag=0, cin_stride=64 + self.c8)[:, :64 + self.c]

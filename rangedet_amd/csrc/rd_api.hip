@@ -12,6 +12,7 @@
 #include "k_riou.h"
 #include "k_loss.h"
 #include "k_convbwd.h"
+#include "k_convbwd_narrow.h"
 #include "k_metabwd.h"
 #include "k_norm.h"
 #include "k_optim.h"
@@ -1327,6 +1328,119 @@ int rd_conv1x1_bwd_weight(const void* x, int x_cstride, int x_coff, const void* 
   return check_launch("conv1x1_bwd_weight");
 }
 
+// ---- weight gradient of the convs that read the range image (k_convbwd_narrow.h) ----------------------------------------------------------
+static bool nw_slot_ok(int cs, int co) { return cs > 0 && cs % 8 == 0 && co >= 0 && co % 8 == 0 && co + NW_SLOT <= cs; }
+// the checks of rd_conv_bwd_weight_narrow, all of them before any launch (the concat call runs them for its x2 half first)
+static int nw_check(const char* what, const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, const float* dW,
+                    int dw_cin_stride, int dw_cin_off, int B, int H, int W, int cin, int cout, int ksize, int split, int dtype, const void* ws,
+                    size_t ws_bytes) {
+  RD_REQUIRE(x && dz && dW && ws, RD_EINVAL, "%s: null pointer", what);
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "%s: dtype %d (RD_BF16 or RD_F16)", what, dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "%s: split %d (0: the library's choice)", what, split);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "%s: B %d, H %d, W %d", what, B, H, W);
+  RD_REQUIRE(ksize == 1 || ksize == 3, RD_ESHAPE, "%s: ksize %d (1 or 3)", what, ksize);
+  RD_REQUIRE(nw_shape_ok(cin, cout, ksize), RD_ESHAPE, "%s: cin %d (1 .. 16), cout %d (64 or 128)", what, cin, cout);
+  RD_REQUIRE(nw_slot_ok(x_cstride, x_coff) && nhwc16_ok(dz_cstride, dz_coff, cout), RD_ESHAPE,
+             "%s: channel strides and offsets are multiples of 8 with x_coff + 16 <= x_cstride (the whole slot is read) and dz_coff + cout <= "
+             "dz_cstride", what);
+  RD_REQUIRE(dw_cin_off >= 0 && dw_cin_off + cin <= dw_cin_stride, RD_ESHAPE, "%s: dW channels [%d, %d) of %d", what, dw_cin_off, dw_cin_off + cin,
+             dw_cin_stride);
+  RD_REQUIRE(((uintptr_t)x | (uintptr_t)dz) % 16 == 0 && ((uintptr_t)ws | (uintptr_t)dW) % 4 == 0, RD_EINVAL,
+             "%s: x and dz must be 16-byte aligned, dW and the workspace 4-byte aligned", what);
+  const size_t need = nw_ws_bytes(B, H, W, cin, cout, ksize, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+  RD_REQUIRE(nw_split(B, H, W, split) <= 0x7fffffffL, RD_ESHAPE, "%s: split %ld", what, nw_split(B, H, W, split));
+  return RD_OK;
+}
+static void nw_launch(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride,
+                      int dw_cin_off, int B, int H, int W, int cin, int cout, int ksize, int split, int dtype, void* ws, hipStream_t st) {
+  const long S = nw_split(B, H, W, split);
+  NarrowWArgs a;
+  a.x = (const unsigned short*)x; a.dz = (const unsigned short*)dz;
+  a.x_cs = x_cstride; a.x_co = x_coff; a.dz_cs = dz_cstride; a.dz_co = dz_coff;
+  a.B = B; a.H = H; a.W = W; a.nwt = (W + NW_PT - 1) / NW_PT; a.nhs = (H + NW_RH - 1) / NW_RH; a.cin = cin;
+  a.nchunks = nw_chunks(B, H, W);
+  a.part = (float*)ws;
+  const dim3 grid((unsigned)S);
+  if (ksize == 3 && cout == 128) RD_LAUNCH_H16(dtype, (conv_bwd_weight_narrow_kernel<DT, 128, 3>), grid, dim3(256), st, a);
+  else if (ksize == 3) RD_LAUNCH_H16(dtype, (conv_bwd_weight_narrow_kernel<DT, 64, 3>), grid, dim3(256), st, a);
+  else if (cout == 128) RD_LAUNCH_H16(dtype, (conv_bwd_weight_narrow_kernel<DT, 128, 1>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv_bwd_weight_narrow_kernel<DT, 64, 1>), grid, dim3(256), st, a);
+  const int nt = ksize * ksize;
+  hipLaunchKernelGGL(bwd_weight_reduce_strided_kernel, dim3((nt * cout * cin + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin,
+                     dW, nt, dw_cin_stride, dw_cin_off);
+}
+size_t rd_conv_bwd_weight_narrow_workspace_bytes(int B, int H, int W, int cin, int cout, int ksize, int split) {
+  return bhw_ok(B, H, W) && split >= 0 && nw_shape_ok(cin, cout, ksize) ? nw_ws_bytes(B, H, W, cin, cout, ksize, split) : 0;
+}
+int rd_conv_bwd_weight_narrow(const void* x, int x_cstride, int x_coff, const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride,
+                              int dw_cin_off, int B, int H, int W, int cin, int cout, int ksize, int split, int dtype, void* ws, size_t ws_bytes,
+                              void* stream) {
+  const int rc = nw_check("conv_bwd_weight_narrow", x, x_cstride, x_coff, dz, dz_cstride, dz_coff, dW, dw_cin_stride, dw_cin_off, B, H, W, cin, cout,
+                          ksize, split, dtype, ws, ws_bytes);
+  if (rc != RD_OK) return rc;
+  nw_launch(x, x_cstride, x_coff, dz, dz_cstride, dz_coff, dW, dw_cin_stride, dw_cin_off, B, H, W, cin, cout, ksize, split, dtype, ws,
+            (hipStream_t)stream);
+  return check_launch("conv_bwd_weight_narrow");
+}
+
+// The weight gradient of the concat conv [x1 | x2] -> cout (the level-0 conv_0): channels [0, cin1) are rd_conv3x3_bwd_weight's kernel on
+// (x1, dz) with its reduce writing at the channel stride cin1 + cin2, channels [cin1, cin1 + cin2) the narrow kernel on (x2, dz).  The
+// workspace holds the partial images of the first, then those of the second.
+size_t rd_conv3x3_bwd_weight_cat_workspace_bytes(int B, int H, int W, int cin1, int cin2, int cout, int split) {
+  if (!(bhw_ok(B, H, W) && split >= 0 && cin1 == 64 && nw_shape_ok(cin2, cout, 3))) return 0;
+  return bw_weight_ws_bytes(B, H, W, cin1, cout, split) + nw_ws_bytes(B, H, W, cin2, cout, 3, split);
+}
+static int bw_cat_run(const char* what, const void* x1, int x1_cstride, int x1_coff, int cin1, const void* x2, int x2_cstride, int x2_coff,
+                      int cin2, const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride, int B, int H, int W, int cout, int split,
+                      int dtype, void* ws, size_t ws_bytes, void* stream) {
+  RD_REQUIRE(x1 && x2 && dz && dW && ws, RD_EINVAL, "%s: null pointer", what);
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "%s: dtype %d (RD_BF16 or RD_F16)", what, dtype);
+  RD_REQUIRE(split >= 0, RD_EINVAL, "%s: split %d (0: the library's choice)", what, split);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "%s: B %d, H %d, W %d", what, B, H, W);
+  RD_REQUIRE(cin1 == 64, RD_ESHAPE, "%s: cin1 %d (64: the agg3 feature map)", what, cin1);
+  RD_REQUIRE(nw_shape_ok(cin2, cout, 3), RD_ESHAPE, "%s: cin2 %d (1 .. 16), cout %d (64 or 128)", what, cin2, cout);
+  const size_t need1 = bw_weight_ws_bytes(B, H, W, cin1, cout, split), need = need1 + nw_ws_bytes(B, H, W, cin2, cout, 3, split);
+  RD_REQUIRE(nhwc16_ok(x1_cstride, x1_coff, cin1), RD_ESHAPE, "%s: x1 channel stride and offset are multiples of 8 with coff + 64 <= cstride", what);
+  RD_REQUIRE((uintptr_t)x1 % 16 == 0, RD_EINVAL, "%s: x1 must be 16-byte aligned", what);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+  void* ws2 = (char*)ws + need1;
+  const int rc = nw_check(what, x2, x2_cstride, x2_coff, dz, dz_cstride, dz_coff, dW, dw_cin_stride, cin1, B, H, W, cin2, cout, 3, split, dtype, ws2,
+                          ws_bytes - need1);
+  if (rc != RD_OK) return rc;
+  const long S = bw_split(B, H, W, cout, split);
+  RD_REQUIRE(S <= 0x7fffffffL, RD_ESHAPE, "%s: split %ld", what, S);
+  BwdWArgs a;
+  a.x = (const unsigned short*)x1; a.dz = (const unsigned short*)dz;
+  a.x_cs = x1_cstride; a.x_co = x1_coff; a.dz_cs = dz_cstride; a.dz_co = dz_coff;
+  a.B = B; a.H = H; a.W = W; a.nwt = (W + BW_PT - 1) / BW_PT; a.nhs = (H + BW_RH - 1) / BW_RH;
+  a.nchunks = bw_chunks(B, H, W);
+  a.part = (float*)ws;
+  a.Wz = W;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, 3, cout / BW_COB);
+  if (cout == 128) RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 128>), grid, dim3(256), st, a);
+  else RD_LAUNCH_H16(dtype, (conv3_bwd_weight_kernel<DT, 64, 64>), grid, dim3(256), st, a);
+  hipLaunchKernelGGL(bwd_weight_reduce_strided_kernel, dim3((9 * cout * cin1 + 255) / 256), dim3(256), 0, st, (const float*)ws, (int)S, cout, cin1,
+                     dW, 9, dw_cin_stride, 0);
+  nw_launch(x2, x2_cstride, x2_coff, dz, dz_cstride, dz_coff, dW, dw_cin_stride, cin1, B, H, W, cin2, cout, 3, split, dtype, ws2, st);
+  return check_launch(what);
+}
+int rd_conv3x3_bwd_weight_cat(const void* x1, int x1_cstride, int x1_coff, int cin1, const void* x2, int x2_cstride, int x2_coff, int cin2,
+                              const void* dz, int dz_cstride, int dz_coff, float* dW, int B, int H, int W, int cout, int split, int dtype,
+                              void* ws, size_t ws_bytes, void* stream) {
+  return bw_cat_run("conv3x3_bwd_weight_cat", x1, x1_cstride, x1_coff, cin1, x2, x2_cstride, x2_coff, cin2, dz, dz_cstride, dz_coff, dW, cin1 + cin2, B,
+                    H, W, cout, split, dtype, ws, ws_bytes, stream);
+}
+// the same into a gradient whose channel stride is wider than cin1 + cin2 (a master padded to the width the forward reads): channels
+// [cin1 + cin2, dw_cin_stride) are never written
+int rd_conv3x3_bwd_weight_cat_padded(const void* x1, int x1_cstride, int x1_coff, int cin1, const void* x2, int x2_cstride, int x2_coff, int cin2,
+                                     const void* dz, int dz_cstride, int dz_coff, float* dW, int dw_cin_stride, int B, int H, int W, int cout,
+                                     int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  return bw_cat_run("conv3x3_bwd_weight_cat_padded", x1, x1_cstride, x1_coff, cin1, x2, x2_cstride, x2_coff, cin2, dz, dz_cstride, dz_coff, dW,
+                    dw_cin_stride, B, H, W, cout, split, dtype, ws, ws_bytes, stream);
+}
+
 size_t rd_head_out_bwd_workspace_bytes(int B, int H, int W, int cin, int nout) {
   return bhw_ok(B, H, W) && (cin == 64 || cin == 128) && nout >= 1 && nout <= 8 ? hob_ws_bytes((long)B * H * W, cin) : 0;
 }
@@ -1596,6 +1710,35 @@ int rd_pack_conv3x3_dev(const float* w_dev, const float* fold_scale_dev, int cou
   RD_LAUNCH_H16(dtype, (pack_conv3x3_dev_kernel<DT>), dim3(grid), dim3(256), (hipStream_t)stream, w_dev, fold_scale_dev, cout, cin, flip ? 1 : 0,
                 (unsigned short*)out_dev);
   return check_launch("pack_conv3x3_dev");
+}
+
+// ---- launch images of the narrow-input convs from device-resident masters (k_convbwd_narrow.h) ------------------------------------------
+static int nwp_launch(const char* what, const float* w_dev, const float* fold_scale_dev, int cout, int cin, int mode, int dtype, void* out_dev,
+                      void* stream) {
+  RD_REQUIRE((uintptr_t)out_dev % 16 == 0 && ((uintptr_t)w_dev | (uintptr_t)fold_scale_dev) % 4 == 0, RD_EINVAL,
+             "%s: the image must be 16-byte aligned, the float buffers 4-byte aligned", what);
+  const long body = nwp_body_slots(mode, cout), total = nwp_total_slots(mode, cout, cin, dtype);
+  RD_LAUNCH_H16(dtype, (pack_narrow_dev_kernel<DT>), dim3((unsigned)((total + SGD_PACK_SLOTS - 1) / SGD_PACK_SLOTS)), dim3(256), (hipStream_t)stream,
+                w_dev, fold_scale_dev, cout, cin, mode, body, total, (unsigned short*)out_dev);
+  return check_launch(what);
+}
+int rd_pack_conv_narrow_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin, int ksize, int dtype, void* out_dev, void* stream) {
+  RD_REQUIRE(w_dev && out_dev, RD_EINVAL, "pack_conv_narrow_dev: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_conv_narrow_dev: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(ksize == 1 || ksize == 3, RD_ESHAPE, "pack_conv_narrow_dev: ksize %d (1 or 3)", ksize);
+  RD_REQUIRE(nw_shape_ok(cin, cout, ksize), RD_ESHAPE, "pack_conv_narrow_dev: cin %d (1 .. 16), cout %d (64 or 128)", cin, cout);
+  RD_REQUIRE(!(ksize == 1 && fold_scale_dev), RD_EINVAL, "pack_conv_narrow_dev: the 1x1 image takes no fold scale");
+  return nwp_launch("pack_conv_narrow_dev", w_dev, fold_scale_dev, cout, cin, ksize == 3 ? NWP_NARROW3 : NWP_NARROW1, dtype, out_dev, stream);
+}
+int rd_pack_conv3x3_cat_dev(const float* w_dev, const float* fold_scale_dev, int cout, int cin1, int cin2, int data_grad, int dtype,
+                            void* out_dev, void* stream) {
+  RD_REQUIRE(w_dev && out_dev, RD_EINVAL, "pack_conv3x3_cat_dev: null pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_conv3x3_cat_dev: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(cin1 == NWP_CIN1, RD_ESHAPE, "pack_conv3x3_cat_dev: cin1 %d (64: the agg3 feature map)", cin1);
+  RD_REQUIRE(nw_shape_ok(cin2, cout, 3), RD_ESHAPE, "pack_conv3x3_cat_dev: cin2 %d (1 .. 16), cout %d (64 or 128)", cin2, cout);
+  RD_REQUIRE(data_grad || cin2 % 8 == 0, RD_ESHAPE, "pack_conv3x3_cat_dev: cin2 %d (the forward reads a multiple of 8)", cin2);
+  RD_REQUIRE(!(data_grad && fold_scale_dev), RD_EINVAL, "pack_conv3x3_cat_dev: the data-gradient image takes no fold scale");
+  return nwp_launch("pack_conv3x3_cat_dev", w_dev, fold_scale_dev, cout, cin1 + cin2, data_grad ? NWP_CAT_BWD : NWP_CAT_FWD, dtype, out_dev, stream);
 }
 
 // the data gradient of a transposed conv as a 3x3 stride-1 conv over dz read as [H][Win][s Cout]: its weight image, host and device

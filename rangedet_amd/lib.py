@@ -152,6 +152,14 @@ SIGNATURES = {
     "rd_conv1x1_bwd_weight_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rd_conv1x1_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_conv_bwd_weight_narrow_workspace_bytes": (c_size_t, [c_int] * 7),
+    "rd_conv_bwd_weight_narrow": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_int] * 8
+                                  + [c_void_p, c_size_t, c_void_p]),
+    "rd_conv3x3_bwd_weight_cat_workspace_bytes": (c_size_t, [c_int] * 7),
+    "rd_conv3x3_bwd_weight_cat": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
+                                  + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "rd_conv3x3_bwd_weight_cat_padded": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
+                                         + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
     "rd_deconv_bwd_weight_workspace_bytes": (c_size_t, [c_int] * 9),
     "rd_deconv_bwd_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
@@ -181,6 +189,8 @@ SIGNATURES = {
     "rd_sgd_table_host": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "rd_sgd_mom_update": (c_int, [c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p]),
     "rd_pack_conv3x3_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rd_pack_conv_narrow_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rd_pack_conv3x3_cat_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rd_prof_enable": (c_int, [c_int]),
     "rd_prof_reset": (c_int, []),
     "rd_prof_get": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_long)]),

@@ -130,7 +130,11 @@ class SGD:
         pack = dict(deconv=(KW, stride, pad), fwd=, bwd=, dtype=[, phase_bytes=]) on a (Cin, Cout, 3, KW) transposed-conv weight: the table
         updates the master as a plain tensor without images, and step() then issues one rd_pack_deconv_dev launch per named image on the
         same stream -- fwd, the `stride` phase images rd_deconv2d_bn_act_all reads (phase_bytes apart; default: packed back to back), and
-        bwd, the image of the data gradient.  Nothing synchronises."""
+        bwd, the image of the data gradient.  Nothing synchronises.
+        The convs that read the range image follow the same precedent -- a plain tensor of the table, then one packer launch per image:
+        pack = dict(narrow=ksize, fwd=, dtype=[, fold_scale=]) on a (cout, cin, k, k) weight with cin <= 16 (rd_pack_conv_narrow_dev; the 1x1
+        image takes no fold scale), and pack = dict(cat=(cin1, cin2), fwd=, bwd=, dtype=[, fold_scale=]) on the (cout, 64 + cin2, 3, 3)
+        concat weight (rd_pack_conv3x3_cat_dev: fwd the concat forward image, bwd the data-gradient image towards x1)."""
         _check_f32(weight, name)
         _check_f32(grad, name + " gradient")
         n = _numel(weight)
@@ -153,6 +157,29 @@ class SGD:
             for k in ("fwd", "bwd"):
                 if e["deconv"][k] is not None and rdlib.ptr(e["deconv"][k]) % 16:
                     raise ValueError("%s: %s buffer at %#x is not 16-byte aligned" % (name, k, rdlib.ptr(e["deconv"][k])))
+        elif pack is not None and (pack.get("narrow") is not None or pack.get("cat") is not None):
+            # the convs that read the range image: plain n-element tensors of the table; step() re-packs their images afterwards
+            shp = e["shape"]
+            dt = pack.get("dtype", rdlib.RD_BF16)
+            if dt not in rdlib.H16 or self._dtype not in (None, dt):
+                raise ValueError("%s: image type %r; one 16-bit type (RD_BF16 / RD_F16) per optimizer" % (name, dt))
+            if pack.get("narrow") is not None:
+                k = int(pack["narrow"])
+                if k not in (1, 3) or len(shp) != 4 or shp[2:] != (k, k) or shp[0] not in (64, 128) or not 1 <= shp[1] <= 16:
+                    raise NotImplementedError("%s: narrow=%r images of a %r weight -- a (cout, cin, k, k) weight with k 1 or 3, cin 1 .. 16, cout "
+                                              "64 or 128" % (name, pack["narrow"], shp))
+                if pack.get("bwd") is not None or (k == 1 and pack.get("fold_scale") is not None):
+                    raise ValueError("%s: a narrow conv has no data-gradient image, and its 1x1 image takes no fold scale" % name)
+                e["repack"] = dict(kind="narrow", form=(shp[0], shp[1], k), fwd=pack.get("fwd"), bwd=None, fold=pack.get("fold_scale"), dtype=dt)
+            else:
+                cin1, cin2 = (int(v) for v in pack["cat"])
+                if len(shp) != 4 or shp[2:] != (3, 3) or shp[0] not in (64, 128) or cin1 != 64 or cin2 not in (8, 16) or shp[1] != cin1 + cin2:
+                    raise NotImplementedError("%s: cat=%r images of a %r weight -- a (cout, 64 + cin2, 3, 3) weight with cin2 8 or 16, cout 64 or "
+                                              "128" % (name, tuple(pack["cat"]), shp))
+                e["repack"] = dict(kind="cat", form=(shp[0], cin1, cin2), fwd=pack.get("fwd"), bwd=pack.get("bwd"), fold=pack.get("fold_scale"), dtype=dt)
+            for k in ("fwd", "bwd", "fold"):
+                if e["repack"][k] is not None and rdlib.ptr(e["repack"][k]) % (4 if k == "fold" else 16):
+                    raise ValueError("%s: %s buffer at %#x is not aligned" % (name, k, rdlib.ptr(e["repack"][k])))
         elif pack is not None:
             shp = e["shape"]
             if len(shp) != 4 or shp[2:] not in ((3, 3), (1, 1)) or shp[0] not in (64, 128) or shp[1] not in (64, 128):
@@ -218,4 +245,16 @@ class SGD:
                 if d[key] is not None:
                     self.L.call("rd_pack_deconv_dev", rdlib.ptr(e["weight"]), *d["form"], data_grad, d["phase_bytes"], d["dtype"],
                                 rdlib.ptr(d[key]), stream)
+        for e in self._entries.values():          # the narrow and the concat conv's images: one launch each, likewise
+            r = e.get("repack")
+            if r is None:
+                continue
+            fold = None if r["fold"] is None else rdlib.ptr(r["fold"])
+            if r["kind"] == "narrow" and r["fwd"] is not None:
+                self.L.call("rd_pack_conv_narrow_dev", rdlib.ptr(e["weight"]), fold, *r["form"], r["dtype"], rdlib.ptr(r["fwd"]), stream)
+            if r["kind"] == "cat":
+                for key, data_grad in (("fwd", 0), ("bwd", 1)):
+                    if r[key] is not None:
+                        self.L.call("rd_pack_conv3x3_cat_dev", rdlib.ptr(e["weight"]), None if data_grad else fold, *r["form"], data_grad,
+                                    r["dtype"], rdlib.ptr(r[key]), stream)
         return lr
