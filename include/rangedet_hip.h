@@ -530,8 +530,8 @@ int rd_rpn_loss(const float* logit, long logit_bstride, const float* delta, long
  * 2 cin).  The network's own transposed convs: rd_deconv_bwd_weight and the packers declared with it.  The Meta-Kernel unit
  * with the folded normalisation: rd_meta_kernel_bwd_data and rd_meta_kernel_bwd_params, at the end of this section.  The convs that read the
  * range image itself (res1_unit1's conv1 and projection, the level-0 concat conv): rd_conv_bwd_weight_narrow and
- * rd_conv3x3_bwd_weight_cat below, their device packers with the optimizer's.  Not here: the batch-statistics form of the Meta-Kernel's
- * 576-channel BatchNorm, and a device re-pack of that unit.
+ * rd_conv3x3_bwd_weight_cat below, their device packers with the optimizer's.  The batch-statistics form of the Meta-Kernel's
+ * 576-channel BatchNorm and the device re-pack of that unit follow the frozen form: rd_meta_kernel_stats .. rd_pack_meta_dev.
  *
  * rd_relu_affine_bwd: dz = round(float(g) * s[c]) where y > 0, else +0 -- one float32 product, one rounding.  y == NULL: no mask;
  * scale == NULL: 1 (a later normalisation-backward launch then feeds the conv primitives with y = scale = NULL).  C a multiple of 8.
@@ -661,6 +661,45 @@ size_t rd_meta_kernel_bwd_workspace_bytes(int B, int H, int W, int split);
 int rd_meta_kernel_bwd_params(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
                               const void* packed_bwd, float* dA, float* dW1, float* db1, float* dW0, float* db0, float* dt1, float* dq1, int B,
                               int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* The Meta-Kernel unit in TRAINING mode: the 576-channel BatchNorm normalises q_k[c] = data[n_k][c] * w_k[c] with the batch's own
+ * statistics (use_global_stats = False).  RD_BF16 / RD_F16 only (RD_F32: RD_EINVAL).  Every launch reads the packed blocks made with
+ * s1 = s2 = 1, t1 = t2 = 0 -- packed_fwd: rd_pack_meta_host's, packed_bwd: rd_pack_meta_bwd_host's, or both from rd_pack_meta_dev -- so a
+ * block depends on the parameters only, and takes the normalisation as float32 device vectors of 576 values, index c 9 + k, however they
+ * were computed: a1 = gamma1 rstd1, bb1 = fmaf(-mean1, a1, beta1) (rd_bn_fold with C = 576 on rd_meta_kernel_stats' output), mean1, rstd1,
+ * c1 = dbeta1 / n, c2 = dgamma1 / n (n = B H W).  The arithmetic and every 16-bit rounding point: csrc/k_metatrain.h, k_metabwd.h.
+ *   rd_meta_kernel_stats             mean1, var1 (biased, 576 each) over all n pixels of q; a padded tap counts with q = 0.  Sums shifted by
+ *                                    a per-workgroup pilot, per-workgroup partials, a fixed-order merge launch.
+ *   rd_meta_kernel_fwd_train         z (B, H, W, 64 at z_coff) = round(sum A relu(round(fmaf(q, a1, bb1)))): no affine, no ReLU; the second
+ *                                    BatchNorm is rd_bn_stats, rd_bn_fold, rd_affine_relu with C = 64 on z.
+ *   rd_meta_kernel_bwd_sums          pass A, dz from rd_bn_relu_bwd(g, z, ..): dA (64, 576), dbeta1, dgamma1 (576: the gradients of the
+ *                                    BatchNorm's beta and gamma), c1, c2 (576)
+ *   rd_meta_kernel_bwd_params_train  pass B: dW1 (64, 32), db1 (64), dW0 (32, 3), db0 (32)
+ *   rd_meta_kernel_bwd_data_train    ddata in the activation type, rounded once; residual as in rd_meta_kernel_bwd_data
+ *   rd_pack_meta_dev                 both blocks from the device-resident float32 masters w0 (32, 3), b0 (32), w1 (64, 32), b1 (64),
+ *                                    agg (64, 576): byte for byte the host packers' output for s1 = s2 = 1, t1 = t2 = 0
+ * split as in rd_meta_kernel_bwd_params; the workspaces hold split x 9 x 256 (statistics) and split x 9 x 4224 (pass A and pass B) floats
+ * at most, partial sums only.  No atomics, two calls give the same bytes, the bytes do not depend on the CU count.  Status codes as above. */
+size_t rd_meta_kernel_stats_workspace_bytes(int B, int H, int W, int split);
+int rd_meta_kernel_stats(const void* data, int d_cstride, int d_coff, const float* coord_nchw, const void* packed_bwd, float* mean1,
+                         float* var1, int B, int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+int rd_meta_kernel_fwd_train(const void* data, int d_cstride, int d_coff, const float* coord_nchw, const void* packed_fwd,
+                             const void* packed_bwd, const float* a1, const float* bb1, void* z, int z_cstride, int z_coff, int B, int H,
+                             int W, int dtype, void* stream);
+size_t rd_meta_kernel_bwd_train_workspace_bytes(int B, int H, int W, int split);
+int rd_meta_kernel_bwd_sums(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                            const void* packed_bwd, const float* a1, const float* bb1, const float* mean1, const float* rstd1, float* dA,
+                            float* dbeta1, float* dgamma1, float* c1, float* c2, int B, int H, int W, int split, int dtype, void* ws,
+                            size_t ws_bytes, void* stream);
+int rd_meta_kernel_bwd_params_train(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff,
+                                    const float* coord_nchw, const void* packed_bwd, const float* a1, const float* bb1, const float* mean1,
+                                    const float* rstd1, const float* c1, const float* c2, float* dW1, float* db1, float* dW0, float* db0,
+                                    int B, int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream);
+int rd_meta_kernel_bwd_data_train(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff,
+                                  const float* coord_nchw, const void* packed_bwd, const float* a1, const float* bb1, const float* mean1,
+                                  const float* rstd1, const float* c1, const float* c2, const void* residual, int r_cstride, int r_coff,
+                                  void* ddata, int g_cstride, int g_coff, int B, int H, int W, int dtype, void* stream);
+int rd_pack_meta_dev(const float* w0, const float* b0, const float* w1, const float* b1, const float* agg, void* packed_fwd,
+                     void* packed_bwd, int dtype, void* stream);
 
 /* ---- training-mode batch norm of a head-tower layer, forward and backward ----------------------------------------------------------------
  * The reference builds every tower layer with normalizer_factory(type="localbn") (mxnext/complicate.py:26-45): mx.sym.BatchNorm with

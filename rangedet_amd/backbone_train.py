@@ -565,3 +565,104 @@ class ResStageTrain:
         for b in self.blocks:
             out.update(b.aux())
         return out
+
+
+class MetaBlockTrain(_BlockTrain):
+    """res1_unit2 as the reference trains it: the BasicBlock whose first conv is the Meta-Kernel (dla_backbone.py:92-97).
+    rangedet_amd.backward.MetaUnitTrain stands in for conv1 + bn1 + relu1 -- both of its BatchNorms with the batch's own statistics --
+    then conv2, bn2, the identity add and the ReLU are BasicBlockTrain's steps.
+      name, params, W    the unit's name, the reference's parameter dict (arguments and auxiliary states in one dict) and the width the
+                         MLP's parameter names carry: <name>_<W>_mlp0|1_weight|bias, <name>point_wise_mlp_bn1_*, <name>aggregation_conv1_weight,
+                         <name>aggregation_bn1_*, <name>_conv2_weight, <name>_bn2_*
+    forward(x, coord) -> y, x (B, H, W, 64), coord (B, 3, H, W) float32; backward(g) -> (dx, grads): the shortcut's gradient goes in as the
+    residual of the Meta-Kernel's data-gradient launch, so dx is rounded once.  aux() and optimizer_entries() chain the unit's."""
+
+    def __init__(self, name, params, W, dtype=rdlib.RD_BF16, eps=BN_EPS, momentum=BN_MOMENTUM, lib=None, alloc=None):
+        from .backward import MetaUnitTrain
+        w2 = np.ascontiguousarray(params[name + "_conv2_weight"], dtype=np.float32)
+        if w2.shape != (64, 64, 3, 3):
+            raise ValueError("%s: conv2 is a (64, 64, 3, 3) weight, got %r" % (name, w2.shape))
+        self.name = name
+        self.meta = MetaUnitTrain(name, params, W, eps=eps, momentum=momentum, dtype=dtype, lib=lib, alloc=alloc)
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        self.cin = self.cout = 64
+        self.proj = False
+        self.eps, self.momentum = float(eps), float(momentum)
+        self.convs = {"conv2": dict(cin=64, cout=64, fwd=o.pack_unscaled(w2), bwd=o.pack_data_grad(w2), master=o.A.upload(w2))}
+        self.bns = {"bn2": self._bn(tuple(params["%s_bn2_%s" % (name, k)] for k in _BN_KEYS), "bn2")}
+        self.x = self.saved = None
+
+    def forward(self, x, coord, unbiased=True):
+        o, cv = self.ops, self.convs
+        y1 = self.meta.forward(x, coord, unbiased)
+        z2 = o.conv_unscaled(y1, cv["conv2"]["fwd"], 64, 64, tag=2)
+        saved = {"bn2": self._norm(z2, "bn2", 2, unbiased)}
+        y = o.affine_add_relu(z2, saved["bn2"]["a"], saved["bn2"]["b"], x)
+        self.x, self.y1, self.z2, self.saved, self.y = x, y1, z2, saved, y
+        return y
+
+    def backward(self, g):
+        if self.x is None:
+            raise RuntimeError("backward before forward: the activations are kept by forward(x, coord)")
+        o, cv, nm = self.ops, self.convs, self.name
+        grads = {}
+        dz2, dr, grads[nm + "_bn2_gamma"], grads[nm + "_bn2_beta"], _, _ = o.bn_add_relu_bwd(g, self.z2, self.x, self.saved["bn2"],
+                                                                                             self.bns["bn2"]["gamma"], None, None, tag=2)
+        grads[nm + "_conv2_weight"] = o.weight_grad(self.y1, dz2, tag=2)
+        g1 = o.data_grad(dz2, cv["conv2"]["bwd"], tag=2)
+        dx, gm = self.meta.backward(g1, residual=dr)
+        grads.update(gm)
+        self.g, self.dz2, self.dr, self.g1, self.dx = g, dz2, dr, g1, dx
+        return dx, grads
+
+    def aux(self):
+        return dict(self.meta.aux(), **super().aux())
+
+    def optimizer_entries(self):
+        o, cv = self.ops, self.convs["conv2"]
+        yield from self.meta.optimizer_entries()
+        yield dict(name=self.name + "_conv2_weight", weight=o.A.view_f32(cv["master"], (64, 64, 3, 3)),
+                   grad=o.A.view_f32(o.buf(("dW", 2), 64 * 64 * 36), (64, 64, 3, 3)), pack=dict(fwd=cv["fwd"][0], bwd=cv["bwd"][0], dtype=o.dt))
+        yield from self._norm_entries("bn2", ("bn_dgamma", 2), ("bn_dbeta", 2))
+
+
+class Res1StageTrain:
+    """The `res1` stage: StemBlockTrain (res1_unit1, on the range-image slot) then MetaBlockTrain (res1_unit2).  forward(x, coord) with x the
+    (B, H, W, 16) range-image slot and coord (B, 3, H, W) float32; backward(g) -> (None, grads): the range image takes no gradient.  The
+    rest is ResStageTrain's interface."""
+
+    def __init__(self, stem, meta):
+        self.blocks = [stem, meta]
+
+    @classmethod
+    def from_params(cls, arg_params, aux_params, W, stage="res1", dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        """from the reference's parameter dicts: <stage>_unit1_* is the stem, <stage>_unit2* the Meta-Kernel unit whose MLP names carry W"""
+        u1, u2 = stage + "_unit1", stage + "_unit2"
+
+        def bn(key):
+            pre = "%s_%s_" % (u1, key)
+            return dict(gamma=arg_params[pre + "gamma"], beta=arg_params[pre + "beta"], moving_mean=aux_params[pre + "moving_mean"],
+                        moving_var=aux_params[pre + "moving_var"])
+        kw = dict(dtype=dtype, lib=lib, alloc=alloc)
+        stem = StemBlockTrain(u1, arg_params[u1 + "_conv1_weight"], arg_params[u1 + "_conv2_weight"], bn("bn1"), bn("bn2"),
+                              arg_params[u1 + "_sc_weight"], bn("sc_bn"), **kw)
+        return cls(stem, MetaBlockTrain(u2, dict(arg_params, **aux_params), W, **kw))
+
+    def forward(self, x, coord, unbiased=True):
+        return self.blocks[1].forward(self.blocks[0].forward(x, unbiased), coord, unbiased)
+
+    def backward(self, g):
+        g, grads = self.blocks[1].backward(g)
+        _, gs = self.blocks[0].backward(g)
+        grads.update(gs)
+        return None, grads
+
+    def optimizer_entries(self):
+        for b in self.blocks:
+            yield from b.optimizer_entries()
+
+    def aux(self):
+        out = {}
+        for b in self.blocks:
+            out.update(b.aux())
+        return out

@@ -583,6 +583,72 @@ class TowerOps:
         self.L.call("rd_meta_kernel_fwd", rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_fwd), A.ptr(out), 64, 0, B, H, W, self.dt, _stream(A))
         return _view16(A, out, (B, H, W, 64), self.dt)
 
+    # ---- the Meta-Kernel unit in training mode (csrc/k_metatrain.h; MetaUnitTrain below).  Tables: float32 device buffers of 576, c 9 + k ----
+    def _meta_train_ws(self, entry, B, H, W, split):
+        nws = self.L.raw(entry)(B, H, W, split)
+        return self.buf(("meta_train_ws", 0), nws), nws
+
+    def meta_stats(self, data, coord, packed_bwd, split=0, tag=0):
+        """-> the buffers mean1, var1 (576, biased) of q = data[n_k] * w_k over all pixels"""
+        A = self.A
+        B, H, W = self._meta_check(data, data, coord, "meta_stats")
+        ws, nws = self._meta_train_ws("rd_meta_kernel_stats_workspace_bytes", B, H, W, split)
+        mean, var = self.buf(("meta_mean1", tag), 576 * 4), self.buf(("meta_var1", tag), 576 * 4)
+        self.L.call("rd_meta_kernel_stats", rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd), A.ptr(mean), A.ptr(var), B, H, W, split,
+                    self.dt, A.ptr(ws), nws, _stream(A))
+        return mean, var
+
+    def meta_forward_train(self, data, coord, packed_fwd, packed_bwd, a1, bb1, tag=0):
+        """-> z (B, H, W, 64): the aggregation conv's output, before its BatchNorm"""
+        A = self.A
+        B, H, W = self._meta_check(data, data, coord, "meta_forward_train")
+        out = self.buf(("meta_z", tag), B * H * W * 128)
+        self.L.call("rd_meta_kernel_fwd_train", rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_fwd), A.ptr(packed_bwd), A.ptr(a1), A.ptr(bb1),
+                    A.ptr(out), 64, 0, B, H, W, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, 64), self.dt)
+
+    def meta_bwd_sums(self, dz, data, coord, packed_bwd, tabs, split=0, tag=0):
+        """pass A.  tabs: the dict of buffers a1, bb1, mean1, rstd1 -> float32 device views dA (64, 576), dbeta1, dgamma1, c1, c2 (576,)"""
+        A = self.A
+        B, H, W = self._meta_check(dz, data, coord, "meta_bwd_sums")
+        ws, nws = self._meta_train_ws("rd_meta_kernel_bwd_train_workspace_bytes", B, H, W, split)
+        shapes = (("dA", (64, 576)), ("dbeta1", (576,)), ("dgamma1", (576,)), ("c1", (576,)), ("c2", (576,)))
+        bufs = [self.buf(("meta_t_" + k, tag), int(np.prod(shp)) * 4) for k, shp in shapes]
+        self.L.call("rd_meta_kernel_bwd_sums", rdlib.ptr(dz), 64, 0, rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd),
+                    *[A.ptr(tabs[k]) for k in ("a1", "bb1", "mean1", "rstd1")], *[A.ptr(b) for b in bufs], B, H, W, split, self.dt, A.ptr(ws), nws,
+                    _stream(A))
+        return {k: A.view_f32(b, shp) for (k, shp), b in zip(shapes, bufs)}
+
+    def meta_bwd_params_train(self, dz, data, coord, packed_bwd, tabs, split=0, tag=0):
+        """pass B.  tabs: a1, bb1, mean1, rstd1, c1, c2 -> float32 device views dW1 (64, 32), db1 (64,), dW0 (32, 3), db0 (32,)"""
+        A = self.A
+        B, H, W = self._meta_check(dz, data, coord, "meta_bwd_params_train")
+        ws, nws = self._meta_train_ws("rd_meta_kernel_bwd_train_workspace_bytes", B, H, W, split)
+        shapes = (("dW1", (64, 32)), ("db1", (64,)), ("dW0", (32, 3)), ("db0", (32,)))
+        bufs = [self.buf(("meta_t_" + k, tag), int(np.prod(shp)) * 4) for k, shp in shapes]
+        self.L.call("rd_meta_kernel_bwd_params_train", rdlib.ptr(dz), 64, 0, rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd),
+                    *[rdlib.ptr(tabs[k]) for k in ("a1", "bb1", "mean1", "rstd1", "c1", "c2")], *[A.ptr(b) for b in bufs], B, H, W, split, self.dt,
+                    A.ptr(ws), nws, _stream(A))
+        return {k: A.view_f32(b, shp) for (k, shp), b in zip(shapes, bufs)}
+
+    def meta_bwd_data_train(self, dz, data, coord, packed_bwd, tabs, residual=None, tag=0):
+        """ddata (B, H, W, 64), rounded once; residual is added in float32 before that rounding"""
+        A = self.A
+        B, H, W = self._meta_check(dz, data, coord, "meta_bwd_data_train")
+        if residual is not None and _check16(residual, "residual") != (B, H, W, 64):
+            raise ValueError("meta_bwd_data_train: residual %r, the input gradient is %r" % (tuple(residual.shape), (B, H, W, 64)))
+        out = self.buf(("meta_t_ddata", tag), B * H * W * 128)
+        self.L.call("rd_meta_kernel_bwd_data_train", rdlib.ptr(dz), 64, 0, rdlib.ptr(data), 64, 0, rdlib.ptr(coord), A.ptr(packed_bwd),
+                    *[rdlib.ptr(tabs[k]) for k in ("a1", "bb1", "mean1", "rstd1", "c1", "c2")], None if residual is None else rdlib.ptr(residual),
+                    64, 0, A.ptr(out), 64, 0, B, H, W, self.dt, _stream(A))
+        return _view16(A, out, (B, H, W, 64), self.dt)
+
+    def pack_meta_dev(self, masters, packed_fwd, packed_bwd):
+        """both blocks of the unit from the float32 device masters w0, b0, w1, b1, agg (a dict), with s1 = s2 = 1 and t1 = t2 = 0"""
+        A = self.A
+        self.L.call("rd_pack_meta_dev", *[rdlib.ptr(masters[k]) for k in ("w0", "b0", "w1", "b1", "agg")], A.ptr(packed_fwd), A.ptr(packed_bwd),
+                    self.dt, _stream(A))
+
 
 BN_EPS = 1e-5 + 1e-10      # mxnext/complicate.py:26-45 (normalizer_factory(type="localbn"))
 BN_MOMENTUM = 0.9
@@ -691,7 +757,8 @@ class MetaUnitBackward:
     csrc/k_metabwd.h; residual (the identity shortcut's gradient) is added to ddata in float32 before its one rounding.  grads: float32
     device tensors under the reference's names and shapes for the two MLP convs and the aggregation conv, and -- under the frozen
     statistics -- point_wise_mlp_bn1_beta = dt1, point_wise_mlp_bn1_gamma = dq1 / gamma.  The gradients of aggregation_bn1's gamma and beta
-    need z, which the fused forward never writes: they come with the training-mode form."""
+    need z, which the fused forward never writes: they come with the training-mode form, MetaUnitTrain below, which also carries the
+    batch-statistics form of the 576-channel BatchNorm, the device re-pack and optimizer_entries()."""
 
     def __init__(self, name, params, W, dtype=rdlib.RD_BF16, lib=None, alloc=None, eps=BN_EPS):
         from .runtime import bn_affine
@@ -733,6 +800,88 @@ class MetaUnitBackward:
                 v = v / self.gamma                 # d r / d gamma = (r - t1) / gamma under the frozen statistics
             grads[pname] = v.reshape(shape)
         return o.meta_data_grad(dz, data, coord, self.packed_bwd, residual), grads
+
+
+class MetaUnitTrain:
+    """The Meta-Kernel unit as the reference trains it: both BatchNorms (the 576-channel point_wise_mlp_bn1 and the 64-channel
+    aggregation_bn1) normalise with the batch's own statistics.  Built from the same parameter dict and names as MetaUnitBackward, plus the
+    four moving statistics.  Every parameter lives on the device as a float32 master; the two packed blocks are made from the masters with
+    s1 = s2 = 1, t1 = t2 = 0 by rd_pack_meta_dev, here and after every optimizer step (optimizer_entries()).
+      forward(data, coord, unbiased=True) -> y (B, H, W, 64): rd_meta_kernel_stats, rd_bn_fold (C = 576), rd_meta_kernel_fwd_train, then
+          rd_bn_stats, rd_bn_fold, rd_affine_relu on z.  unbiased as in batch_norm_relu_forward (n = 1 needs unbiased=False).
+      backward(g, residual=None, split=0) -> (ddata, grads): rd_bn_relu_bwd gives dz and aggregation_bn1's gradients, then pass A
+          (rd_meta_kernel_bwd_sums: dA, point_wise_mlp_bn1's true batch-statistics gradients, c1, c2), pass B
+          (rd_meta_kernel_bwd_params_train) and rd_meta_kernel_bwd_data_train; residual is added to ddata in float32 before its one rounding.
+          grads: float32 device tensors under the reference's eleven names and shapes.
+      aux() -> the four moving statistics by name.  Nothing synchronises with the host."""
+
+    def __init__(self, name, params, W, eps=BN_EPS, momentum=BN_MOMENTUM, dtype=rdlib.RD_BF16, lib=None, alloc=None):
+        self.ops = o = TowerOps(dtype, lib, alloc)
+        A = o.A
+        self.name, self.W, self.eps, self.momentum = name, int(W), float(eps), float(momentum)
+        pre = "%s_%d" % (name, self.W)
+        f = lambda k, shape: np.ascontiguousarray(params[k], dtype=np.float32).reshape(shape)
+        up = lambda k, shape: A.view_f32(A.upload(f(k, shape)), shape)
+        bn1, bn2 = name + "point_wise_mlp_bn1", name + "aggregation_bn1"
+        self.masters = dict(w0=up(pre + "_mlp0_weight", (32, 3)), b0=up(pre + "_mlp0_bias", (32,)), w1=up(pre + "_mlp1_weight", (64, 32)),
+                            b1=up(pre + "_mlp1_bias", (64,)), agg=up(name + "aggregation_conv1_weight", (64, 576)))
+        self.norm = {k: up(k, (C,)) for bn, C in ((bn1, 576), (bn2, 64)) for k in (bn + "_gamma", bn + "_beta", bn + "_moving_mean", bn + "_moving_var")}
+        self.bn1, self.bn2 = bn1, bn2
+        # reference name -> (shape, the master, the TowerOps buffer key backward() writes the gradient to, the gradient's name in backward())
+        self.table = {pre + "_mlp0_weight": ((32, 3, 1, 1), self.masters["w0"], ("meta_t_dW0", 0), "dW0"),
+                      pre + "_mlp0_bias": ((32,), self.masters["b0"], ("meta_t_db0", 0), "db0"),
+                      pre + "_mlp1_weight": ((64, 32, 1, 1), self.masters["w1"], ("meta_t_dW1", 0), "dW1"),
+                      pre + "_mlp1_bias": ((64,), self.masters["b1"], ("meta_t_db1", 0), "db1"),
+                      name + "aggregation_conv1_weight": ((64, 576, 1, 1), self.masters["agg"], ("meta_t_dA", 0), "dA"),
+                      bn1 + "_gamma": ((576,), self.norm[bn1 + "_gamma"], ("meta_t_dgamma1", 0), "dgamma1"),
+                      bn1 + "_beta": ((576,), self.norm[bn1 + "_beta"], ("meta_t_dbeta1", 0), "dbeta1"),
+                      bn2 + "_gamma": ((64,), self.norm[bn2 + "_gamma"], ("bn_dgamma", "meta2"), "dgamma2"),
+                      bn2 + "_beta": ((64,), self.norm[bn2 + "_beta"], ("bn_dbeta", "meta2"), "dbeta2")}
+        self.packed_fwd = A.alloc(o.L.raw("rd_meta_packed_bytes")(dtype))
+        self.packed_bwd = A.alloc(o.L.raw("rd_meta_bwd_packed_bytes")(dtype))
+        o.pack_meta_dev(self.masters, self.packed_fwd, self.packed_bwd)
+        self.saved = None
+
+    def aux(self):
+        return {bn + k: self.norm[bn + k] for bn in (self.bn1, self.bn2) for k in ("_moving_mean", "_moving_var")}
+
+    def optimizer_entries(self):
+        """SGD.add's arguments per trainable parameter; the aggregation weight's entry carries the unit's re-pack request"""
+        o = self.ops
+        for pname, (shape, master, key, _) in self.table.items():
+            n = int(np.prod(shape))
+            kw = dict(name=pname, weight=master.reshape(shape), grad=o.A.view_f32(o.buf(key, n * 4), shape))
+            if pname.endswith("aggregation_conv1_weight"):
+                kw["pack"] = dict(meta=self.masters, fwd=self.packed_fwd, bwd=self.packed_bwd, dtype=o.dt)
+            yield kw
+
+    def forward(self, data, coord, unbiased=True):
+        o, nm = self.ops, self.norm
+        B, H, W, _ = _check16(data, "data")
+        n = B * H * W
+        mean1, var1 = o.meta_stats(data, coord, self.packed_bwd)
+        rstd1, a1, bb1 = o.bn_fold(mean1, var1, nm[self.bn1 + "_gamma"], nm[self.bn1 + "_beta"], nm[self.bn1 + "_moving_mean"],
+                                   nm[self.bn1 + "_moving_var"], n, 576, self.eps, self.momentum, unbiased, tag="meta1")
+        z = o.meta_forward_train(data, coord, self.packed_fwd, self.packed_bwd, a1, bb1)
+        mean2, var2 = o.bn_stats(z, tag="meta2")
+        rstd2, a2, b2 = o.bn_fold(mean2, var2, nm[self.bn2 + "_gamma"], nm[self.bn2 + "_beta"], nm[self.bn2 + "_moving_mean"],
+                                  nm[self.bn2 + "_moving_var"], n, 64, self.eps, self.momentum, unbiased, tag="meta2")
+        self.saved = dict(data=data, coord=coord, z=z, tabs=dict(a1=a1, bb1=bb1, mean1=mean1, var1=var1, rstd1=rstd1),
+                          bn2=dict(a=a2, b=b2, mean=mean2, var=var2, rstd=rstd2))
+        return o.affine_relu(z, a2, b2, tag="meta2")
+
+    def backward(self, g, residual=None, split=0):
+        if self.saved is None:
+            raise RuntimeError("backward before forward: the input, z and the batch statistics are kept by forward(data, coord)")
+        o, s = self.ops, self.saved
+        data, coord, tabs = s["data"], s["coord"], dict(s["tabs"])
+        self.dz, dg2, db2 = o.bn_relu_bwd(g, s["z"], s["bn2"], self.norm[self.bn2 + "_gamma"], split=split, tag="meta2")
+        sums = o.meta_bwd_sums(self.dz, data, coord, self.packed_bwd, tabs, split)
+        tabs.update(c1=sums["c1"], c2=sums["c2"])
+        pg = o.meta_bwd_params_train(self.dz, data, coord, self.packed_bwd, tabs, split)
+        raw = dict(pg, dA=sums["dA"], dgamma1=sums["dgamma1"], dbeta1=sums["dbeta1"], dgamma2=dg2, dbeta2=db2)
+        grads = {pname: raw[rname].reshape(shape) for pname, (shape, _, _, rname) in self.table.items()}
+        return o.meta_bwd_data_train(self.dz, data, coord, self.packed_bwd, tabs, residual), grads
 
 
 class _HeadTower:

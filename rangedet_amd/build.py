@@ -103,6 +103,40 @@ def packed_swap_lint(so=OUT):
         shutil.rmtree(td, ignore_errors=True)
 
 
+# Kernels whose design rests on running without scratch (pass A and pass B of the training-mode Meta-Kernel backward).
+# build() compiles with the compiler's resource remarks on and refuses a library in which one of them spills.
+NO_SCRATCH = ("meta_train_sums_kernel", "meta_train_params_kernel")
+REMARK_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
+_REMARK_NAME = re.compile(r"remark: .*Function Name: (\S+)")
+_REMARK_SCRATCH = re.compile(r"remark: .*ScratchSize \[bytes/lane\]: (\d+)")
+
+
+def scratch_bytes(remarks):
+    """{mangled kernel name: scratch bytes per lane} from the text of -Rpass-analysis=kernel-resource-usage"""
+    out, cur = {}, None
+    for line in remarks.splitlines():
+        m = _REMARK_NAME.search(line)
+        if m:
+            cur = m.group(1)
+            continue
+        m = _REMARK_SCRATCH.search(line)
+        if m and cur is not None:
+            out[cur] = int(m.group(1))
+    return out
+
+
+def check_no_scratch(remarks):
+    """raises if a NO_SCRATCH kernel is missing from the remarks or uses scratch"""
+    sc = scratch_bytes(remarks)
+    for k in NO_SCRATCH:
+        hits = {n: v for n, v in sc.items() if k in n}
+        if not hits:
+            raise RuntimeError("build: no resource remark for %s -- the no-scratch check cannot be made" % k)
+        bad = {n: v for n, v in hits.items() if v}
+        if bad:
+            raise RuntimeError("build: %s uses scratch (%s bytes per lane); it is designed to run without" % (k, sorted(bad.values())))
+
+
 def _stale(out):
     if not os.path.exists(out):
         return True
@@ -116,11 +150,18 @@ def build(force=False, verbose=True):
         return out
     # (a per-process temporary name: several ranks that find the library stale at once must not clobber each other's output)
     tmp_out = "%s.new.%d" % (out, os.getpid())
-    cmd = [_hipcc()] + FLAGS + os.environ.get("RD_EXTRA_HIPCC_FLAGS", "").split() + [SRC, "-o", tmp_out]
+    cmd = [_hipcc()] + FLAGS + REMARK_FLAGS + os.environ.get("RD_EXTRA_HIPCC_FLAGS", "").split() + [SRC, "-o", tmp_out]
     if verbose:
         print(" ".join(cmd), flush=True)
     try:
-        subprocess.check_call(cmd)
+        # (the remarks come on stderr, tens of thousands of lines: kept out of the log, everything else is passed on)
+        proc = subprocess.run(cmd, stderr=subprocess.PIPE, text=True, errors="replace")
+        rest = [ln for ln in proc.stderr.splitlines() if "[-Rpass-analysis=kernel-resource-usage]" not in ln]
+        if rest:
+            print("\n".join(rest), file=sys.stderr, flush=True)
+        if proc.returncode:
+            raise subprocess.CalledProcessError(proc.returncode, cmd)
+        check_no_scratch(proc.stderr)
         bad = packed_swap_lint(tmp_out)
         if bad and not os.environ.get("RD_ALLOW_PACKED_SWAP"):        # (the switch exists for the A/B of the fault itself)
             raise RuntimeError("%s: %d packed-fp32 instructions with swapped source halves (wrong next to MFMA waves on gfx950, "

@@ -39,6 +39,12 @@
 //   (5) e_k = round(dr_k * data[n_k]) as the operand of the dW1 product and of du_k (params kernel; db1 and P4 sum the float32 e_k)
 //   (6) ddata = round(sum + residual), once (data kernel)
 // The centre tap's w_4 is the packer's float32 constant; dz and data are 16-bit inputs.  [u_k > 0] tests the float32 u_k.
+// TRAINING FORM (k_metatrain.h: batch statistics; blocks packed with s1 = 1, t1 = 0; q_k = data[n_k] * w_k, r_k = fmaf(q_k, a1, bb1),
+// dq_k = a1 * fmaf(-xh_k, c2, gy_k - c1)) -- its 16-bit rounding points, everything else float32:
+//   (1) as above; (2) round(W1) and (3) round(A): the packer's values with s1 = 1
+//   (4t) a_k = relu(round(r_k)) as the B operand of z (training forward) and of dA (pass A); the masks [r_k > 0] test the float32 r_k
+//   (5t) e_k = round(dq_k * data[n_k]) as the operand of the dW1 product and of du_k (pass B; db1 and P4 sum the float32 e_k)
+//   (6) ddata = round(sum + residual), once; (7t) z = round(float32 sum), once (training forward)
 #pragma once
 #include "k_meta.h"
 

@@ -14,6 +14,7 @@
 #include "k_convbwd.h"
 #include "k_convbwd_narrow.h"
 #include "k_metabwd.h"
+#include "k_metatrain.h"
 #include "k_norm.h"
 #include "k_optim.h"
 #include "k_sort.h"
@@ -1210,6 +1211,118 @@ int rd_meta_kernel_bwd_params(const void* dz, int dz_cstride, int dz_coff, const
   a.part = (float*)ws;
   const MetaBwdOut out{dA, dW1, db1, dW0, db0, dt1, dq1};
   return launch_meta_bwd_params(a, out, split, dtype, (hipStream_t)stream);
+}
+// ---- the Meta-Kernel unit in training mode (k_metatrain.h) ------------------------------------------------------------------------------
+// data, coord, the backward block, shape and type of every training entry; dz where the entry reads it
+static int meta_train_checks(const char* what, bool has_dz, const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride,
+                             int d_coff, const float* coord, const void* packed, int B, int H, int W, int dtype, MetaTrainArgs& a) {
+  RD_REQUIRE((!has_dz || dz) && data && coord && packed, RD_EINVAL, "%s: null pointer", what);
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "%s: dtype %d (RD_BF16 or RD_F16)", what, dtype);
+  RD_REQUIRE(bhw_ok(B, H, W), RD_ESHAPE, "%s: B %d, H %d, W %d", what, B, H, W);
+  RD_REQUIRE((!has_dz || nhwc16_ok(dz_cstride, dz_coff, 64)) && nhwc16_ok(d_cstride, d_coff, 64), RD_ESHAPE,
+             "%s: channel strides and offsets are multiples of 8 with coff + 64 <= cstride", what);
+  RD_REQUIRE(((uintptr_t)dz | (uintptr_t)data | (uintptr_t)packed) % 16 == 0 && (uintptr_t)coord % 4 == 0, RD_EINVAL,
+             "%s: the tensors and the packed block must be 16-byte aligned, coord 4-byte aligned", what);
+  a = MetaTrainArgs{};
+  a.dz = (const unsigned short*)dz; a.z_cs = dz_cstride; a.z_co = dz_coff;
+  a.data = (const unsigned short*)data; a.d_cs = d_cstride; a.d_co = d_coff;
+  a.coord = coord; a.packed = (const unsigned char*)packed;
+  a.B = B; a.H = H; a.W = W;
+  return RD_OK;
+}
+static bool f32_ok(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!p || (uintptr_t)p % 4 != 0) return false;
+  return true;
+}
+size_t rd_meta_kernel_stats_workspace_bytes(int B, int H, int W, int split) {
+  return bhw_ok(B, H, W) && split >= 0 ? mt_stats_ws_bytes(B, H, W, split) : 0;
+}
+int rd_meta_kernel_stats(const void* data, int d_cstride, int d_coff, const float* coord_nchw, const void* packed_bwd, float* mean1,
+                         float* var1, int B, int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  MetaTrainArgs a;
+  const int rc = meta_train_checks("meta_kernel_stats", false, nullptr, 0, 0, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W, dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(f32_ok({mean1, var1, ws}), RD_EINVAL, "meta_kernel_stats: mean1, var1 and the workspace: non-null, 4-byte aligned");
+  RD_REQUIRE(split >= 0, RD_EINVAL, "meta_kernel_stats: split %d (0: the library's choice)", split);
+  const size_t need = mt_stats_ws_bytes(B, H, W, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "meta_kernel_stats: workspace %zu < %zu bytes", ws_bytes, need);
+  a.part = (float*)ws;
+  return launch_meta_stats(a, mean1, var1, split, dtype, (hipStream_t)stream);
+}
+int rd_meta_kernel_fwd_train(const void* data, int d_cstride, int d_coff, const float* coord_nchw, const void* packed_fwd,
+                             const void* packed_bwd, const float* a1, const float* bb1, void* z, int z_cstride, int z_coff, int B, int H,
+                             int W, int dtype, void* stream) {
+  MetaTrainArgs a;
+  const int rc = meta_train_checks("meta_kernel_fwd_train", false, nullptr, 0, 0, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W, dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(packed_fwd && z && f32_ok({a1, bb1}) && ((uintptr_t)packed_fwd | (uintptr_t)z) % 16 == 0, RD_EINVAL,
+             "meta_kernel_fwd_train: packed_fwd, z (16-byte aligned), a1, bb1 (4-byte aligned): non-null");
+  RD_REQUIRE(nhwc16_ok(z_cstride, z_coff, 64), RD_ESHAPE, "meta_kernel_fwd_train: channel strides and offsets are multiples of 8 with coff + 64 <= cstride");
+  a.packed_fwd = (const unsigned char*)packed_fwd; a.a1 = a1; a.bb1 = bb1;
+  a.ddata = (unsigned short*)z; a.g_cs = z_cstride; a.g_co = z_coff;
+  return launch_meta_fwd_train(a, dtype, (hipStream_t)stream);
+}
+size_t rd_meta_kernel_bwd_train_workspace_bytes(int B, int H, int W, int split) {
+  return bhw_ok(B, H, W) && split >= 0 ? mt_bwd_ws_bytes(B, H, W, split) : 0;
+}
+int rd_meta_kernel_bwd_sums(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff, const float* coord_nchw,
+                            const void* packed_bwd, const float* a1, const float* bb1, const float* mean1, const float* rstd1, float* dA,
+                            float* dbeta1, float* dgamma1, float* c1, float* c2, int B, int H, int W, int split, int dtype, void* ws,
+                            size_t ws_bytes, void* stream) {
+  MetaTrainArgs a;
+  const int rc = meta_train_checks("meta_kernel_bwd_sums", true, dz, dz_cstride, dz_coff, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W, dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(f32_ok({a1, bb1, mean1, rstd1, dA, dbeta1, dgamma1, c1, c2, ws}), RD_EINVAL,
+             "meta_kernel_bwd_sums: the tables, the gradients and the workspace: non-null, 4-byte aligned");
+  RD_REQUIRE(split >= 0, RD_EINVAL, "meta_kernel_bwd_sums: split %d (0: the library's choice)", split);
+  const size_t need = mt_bwd_ws_bytes(B, H, W, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "meta_kernel_bwd_sums: workspace %zu < %zu bytes", ws_bytes, need);
+  a.a1 = a1; a.bb1 = bb1; a.mean1 = mean1; a.rstd1 = rstd1; a.part = (float*)ws;
+  const MetaTrainSumsOut out{dA, dbeta1, dgamma1, c1, c2};
+  return launch_meta_train_sums(a, out, split, dtype, (hipStream_t)stream);
+}
+int rd_meta_kernel_bwd_params_train(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff,
+                                    const float* coord_nchw, const void* packed_bwd, const float* a1, const float* bb1, const float* mean1,
+                                    const float* rstd1, const float* c1, const float* c2, float* dW1, float* db1, float* dW0, float* db0,
+                                    int B, int H, int W, int split, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  MetaTrainArgs a;
+  const int rc = meta_train_checks("meta_kernel_bwd_params_train", true, dz, dz_cstride, dz_coff, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W,
+                                   dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(f32_ok({a1, bb1, mean1, rstd1, c1, c2, dW1, db1, dW0, db0, ws}), RD_EINVAL,
+             "meta_kernel_bwd_params_train: the tables, the gradients and the workspace: non-null, 4-byte aligned");
+  RD_REQUIRE(split >= 0, RD_EINVAL, "meta_kernel_bwd_params_train: split %d (0: the library's choice)", split);
+  const size_t need = mt_bwd_ws_bytes(B, H, W, split);
+  RD_REQUIRE(ws_bytes >= need, RD_EWORKSPACE, "meta_kernel_bwd_params_train: workspace %zu < %zu bytes", ws_bytes, need);
+  a.a1 = a1; a.bb1 = bb1; a.mean1 = mean1; a.rstd1 = rstd1; a.c1 = c1; a.c2 = c2; a.part = (float*)ws;
+  const MetaTrainParamsOut out{dW1, db1, dW0, db0};
+  return launch_meta_train_params(a, out, split, dtype, (hipStream_t)stream);
+}
+int rd_meta_kernel_bwd_data_train(const void* dz, int dz_cstride, int dz_coff, const void* data, int d_cstride, int d_coff,
+                                  const float* coord_nchw, const void* packed_bwd, const float* a1, const float* bb1, const float* mean1,
+                                  const float* rstd1, const float* c1, const float* c2, const void* residual, int r_cstride, int r_coff,
+                                  void* ddata, int g_cstride, int g_coff, int B, int H, int W, int dtype, void* stream) {
+  MetaTrainArgs a;
+  const int rc = meta_train_checks("meta_kernel_bwd_data_train", true, dz, dz_cstride, dz_coff, data, d_cstride, d_coff, coord_nchw, packed_bwd, B, H, W,
+                                   dtype, a);
+  if (rc != RD_OK) return rc;
+  RD_REQUIRE(ddata && f32_ok({a1, bb1, mean1, rstd1, c1, c2}), RD_EINVAL, "meta_kernel_bwd_data_train: ddata and the tables (4-byte aligned): non-null");
+  RD_REQUIRE(nhwc16_ok(g_cstride, g_coff, 64) && (!residual || nhwc16_ok(r_cstride, r_coff, 64)), RD_ESHAPE,
+             "meta_kernel_bwd_data_train: channel strides and offsets are multiples of 8 with coff + 64 <= cstride");
+  RD_REQUIRE(((uintptr_t)ddata | (uintptr_t)residual) % 16 == 0, RD_EINVAL, "meta_kernel_bwd_data_train: ddata and residual must be 16-byte aligned");
+  a.a1 = a1; a.bb1 = bb1; a.mean1 = mean1; a.rstd1 = rstd1; a.c1 = c1; a.c2 = c2;
+  a.res = (const unsigned short*)residual; a.r_cs = r_cstride; a.r_co = r_coff;
+  a.ddata = (unsigned short*)ddata; a.g_cs = g_cstride; a.g_co = g_coff;
+  return launch_meta_train_data(a, dtype, (hipStream_t)stream);
+}
+int rd_pack_meta_dev(const float* w0, const float* b0, const float* w1, const float* b1, const float* agg, void* packed_fwd,
+                     void* packed_bwd, int dtype, void* stream) {
+  RD_REQUIRE(f32_ok({w0, b0, w1, b1, agg}) && packed_fwd && packed_bwd, RD_EINVAL, "pack_meta_dev: null or misaligned pointer");
+  RD_REQUIRE(is_h16(dtype), RD_EINVAL, "pack_meta_dev: dtype %d (RD_BF16 or RD_F16)", dtype);
+  RD_REQUIRE(((uintptr_t)packed_fwd | (uintptr_t)packed_bwd) % 16 == 0, RD_EINVAL, "pack_meta_dev: the packed blocks must be 16-byte aligned");
+  const MetaPackDevArgs a{w0, b0, w1, b1, agg, (unsigned char*)packed_fwd, (unsigned char*)packed_bwd};
+  return launch_meta_pack_dev(a, dtype, (hipStream_t)stream);
 }
 // the same with a stride: stride_w 1 forwards to the entry above (its bytes, its partial count, its workspace); stride_w 2 is the weight
 // gradient of a 3x3 stride-(1,2) pad-1 conv, x (B, H, Win) against dz (B, H, Win / 2): chunks and the split are counted on the dz grid

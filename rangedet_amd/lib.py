@@ -101,6 +101,17 @@ SIGNATURES = {
     "rd_meta_kernel_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rd_meta_kernel_bwd_params": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_void_p] * 7
                                   + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rd_meta_kernel_stats_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rd_meta_kernel_stats": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "rd_meta_kernel_fwd_train": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    "rd_meta_kernel_bwd_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rd_meta_kernel_bwd_sums": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 11 + [c_int] * 5
+                                + [c_void_p, c_size_t, c_void_p]),
+    "rd_meta_kernel_bwd_params_train": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 12 + [c_int] * 5
+                                        + [c_void_p, c_size_t, c_void_p]),
+    "rd_meta_kernel_bwd_data_train": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]
+                                      + [c_int] * 6 + [c_void_p]),
+    "rd_pack_meta_dev": (c_int, [c_void_p] * 7 + [c_int, c_void_p]),
     "rd_sorted_foreground_workspace_bytes": (c_size_t, [c_long, c_long]),
     "rd_sorted_foreground": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

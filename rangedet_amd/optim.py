@@ -134,7 +134,10 @@ class SGD:
         The convs that read the range image follow the same precedent -- a plain tensor of the table, then one packer launch per image:
         pack = dict(narrow=ksize, fwd=, dtype=[, fold_scale=]) on a (cout, cin, k, k) weight with cin <= 16 (rd_pack_conv_narrow_dev; the 1x1
         image takes no fold scale), and pack = dict(cat=(cin1, cin2), fwd=, bwd=, dtype=[, fold_scale=]) on the (cout, 64 + cin2, 3, 3)
-        concat weight (rd_pack_conv3x3_cat_dev: fwd the concat forward image, bwd the data-gradient image towards x1)."""
+        concat weight (rd_pack_conv3x3_cat_dev: fwd the concat forward image, bwd the data-gradient image towards x1).
+        The Meta-Kernel unit likewise: pack = dict(meta=dict(w0=, b0=, w1=, b1=, agg=), fwd=, bwd=, dtype=) on ONE of its five masters (each
+        of them a plain tensor of the table, registered on its own) -- step() issues one rd_pack_meta_dev from the five updated masters into
+        the unit's forward and backward blocks."""
         _check_f32(weight, name)
         _check_f32(grad, name + " gradient")
         n = _numel(weight)
@@ -157,6 +160,24 @@ class SGD:
             for k in ("fwd", "bwd"):
                 if e["deconv"][k] is not None and rdlib.ptr(e["deconv"][k]) % 16:
                     raise ValueError("%s: %s buffer at %#x is not 16-byte aligned" % (name, k, rdlib.ptr(e["deconv"][k])))
+        elif pack is not None and pack.get("meta") is not None:
+            # the Meta-Kernel unit: its five masters are plain tensors of the table; the entry that carries this request (one of the five)
+            # names them all, and step() re-packs the unit's two blocks from them with one rd_pack_meta_dev launch
+            m = pack["meta"]
+            dt = pack.get("dtype", rdlib.RD_BF16)
+            if dt not in rdlib.H16 or self._dtype not in (None, dt):
+                raise ValueError("%s: image type %r; one 16-bit type (RD_BF16 / RD_F16) per optimizer" % (name, dt))
+            want = dict(w0=32 * 3, b0=32, w1=64 * 32, b1=64, agg=64 * 576)
+            if set(m) != set(want) or any(_numel(m[k]) != n_k for k, n_k in want.items()):
+                raise ValueError("%s: meta= names the five float32 masters w0 (32, 3), b0 (32), w1 (64, 32), b1 (64), agg (64, 576)" % name)
+            if pack.get("fwd") is None or pack.get("bwd") is None:
+                raise ValueError("%s: the Meta-Kernel unit's re-pack writes both blocks: fwd= and bwd=" % name)
+            for k, v in m.items():
+                _check_f32(v, "%s: master %s" % (name, k))
+            e["repack"] = dict(kind="meta", masters=dict(m), fwd=pack["fwd"], bwd=pack["bwd"], fold=None, dtype=dt)
+            for k in ("fwd", "bwd"):
+                if rdlib.ptr(e["repack"][k]) % 16:
+                    raise ValueError("%s: %s buffer at %#x is not aligned" % (name, k, rdlib.ptr(e["repack"][k])))
         elif pack is not None and (pack.get("narrow") is not None or pack.get("cat") is not None):
             # the convs that read the range image: plain n-element tensors of the table; step() re-packs their images afterwards
             shp = e["shape"]
@@ -250,6 +271,10 @@ class SGD:
             if r is None:
                 continue
             fold = None if r["fold"] is None else rdlib.ptr(r["fold"])
+            if r["kind"] == "meta":
+                self.L.call("rd_pack_meta_dev", *[rdlib.ptr(r["masters"][k]) for k in ("w0", "b0", "w1", "b1", "agg")], rdlib.ptr(r["fwd"]),
+                            rdlib.ptr(r["bwd"]), r["dtype"], stream)
+                continue
             if r["kind"] == "narrow" and r["fwd"] is not None:
                 self.L.call("rd_pack_conv_narrow_dev", rdlib.ptr(e["weight"]), fold, *r["form"], r["dtype"], rdlib.ptr(r["fwd"]), stream)
             if r["kind"] == "cat":
